@@ -5,7 +5,12 @@ AttNet.infer at the reference's validation shape (B = 4 TTA variants, T = 3 stac
 padded points, fp32) -> TTA softmax/mean/argmax -> scatter to the raw scan -> 8-frame voxel voting.
 Workload = BASELINE.json configs[1] on synthetic 120k-point scans (no SemanticKITTI offline).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the line (`value`, `ms_per_step` = ms of one timed step).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (inputs and weights are seeded: the same
+arguments give the same inputs).  --full adds everything reported beside `value`: the dominant kernel's roofline, the
+raw-scan pipeline, --streams, the stage-2 training step and the CPU baseline.
 
 N > 1: one rank per GPU, each rank streams its OWN sequence (sequence sharding, no collective on the data path) ->
 "scaling": "weak".  Under torch.distributed.run (WORLD_SIZE / RANK in the environment) the ranks are the launcher's; a
@@ -745,6 +750,116 @@ def dry_launch(args):
         print(json.dumps(line), flush=True)
 
 
+def side_measurements(line, args, model, runner, device, dev_frames, ctx, one_step, warm, n_look, value, world):
+    """--full, rank 0, after the timed region: the figures reported beside `value` -- the dominant kernel's roofline from
+    serial steps, the path's executed-FLOP roofline, the instrumented look steps' kernel table, the PCIe-inclusive raw-scan
+    pipeline and (--streams S) S sequences batched on the GPU.  Adds them to `line`."""
+    from streammos_amd import streaming
+    eng = getattr(model, "_engine", None)
+    stem_class_rows = (0, 0, 0, 0)
+    if eng is not None and eng.sparse_stem and eng.stem_w is not None:
+        # occupancy of the frames the timed region cycled through (device-side counts of the stem plan, read here,
+        # outside the timed region): rows per launch of the compact scatter target / the sparse first stage
+        from streammos_amd import ops as _ops
+        metas = [_ops.stem_plan(d["pcds_coord"], *eng.bev_hw).meta.cpu().numpy() for d, _ in dev_frames]
+        stem_class_rows = tuple(float(np.mean([m[8 + c] - m[4 + c] for m in metas])) for c in range(4))
+        ctx["stem_rows"] = float(np.mean([m[11] for m in metas]))
+        ctx["stem_class_rows"] = stem_class_rows
+    roof, families = family_roofline(model, device, dev_frames, args, ctx, one_step)
+    exec_tflop = None
+    if eng is not None and eng.layout == "cl":
+        d0 = dev_frames[0][0]
+        bs, t, _, n = d0["pcds_xyzi"].shape[:4]
+        exec_tflop = executed_flops(eng, bs, n, t, stem_class_rows, ctx.get("live_fraction", 1.0)) / 1e12
+    line.update({
+        "roofline": roof,
+        "path_compute_roofline": (None if exec_tflop is None else
+                                  {"bound": "mfma", "achieved": round(value / world * exec_tflop, 1),
+                                   "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                   "frac": round(value / world * exec_tflop / FP32_PEAK_TFLOPS, 4),
+                                   "executed_tflop_per_scan": round(exec_tflop, 4),
+                                   "dense_equivalent_tflops": round(value / world * ALG_TFLOP_PER_SCAN, 1),
+                                   "note": "scans/s/GPU x the FLOPs the engine really executes per scan (bench.executed_flops "
+                                           "walks the engine's layers and the frames' occupancy) against the fp32 MFMA = "
+                                           "vector peak; dense_equivalent = the reference's 0.53 TFLOP/scan x scans/s, kept for "
+                                           "comparison only (the sparse first stage and the restructured conv_1 skip work)"}),
+        "stem_rows_per_launch": None if ctx.get("stem_rows") is None else round(ctx["stem_rows"]),
+        "stem_class_rows": [round(r) for r in stem_class_rows],
+        "kernel_families_serial": families,
+        "hip_kernel_ms_per_step_warmup": {k: round(v[1] / n_look, 4) for k, v in sorted(warm.items())},
+    })
+    if world == 1 and not args.no_raw:
+        # PCIe-inclusive variant (never `value`): raw scans uploaded every step, preprocessing on the device
+        raw_runner = streaming.StreamRunner(model, device, vote=not args.no_vote, pipeline=not args.no_pipeline,
+                                            skip_padding=not args.no_skip_padding)
+        from streammos_amd import synth as _synth
+        raw = [(_synth.synthetic_scan(k), _synth.synthetic_pose(k)) for k in range(6)]
+        def raw_window(i):
+            idx = [(i + 2) % 4 + 2 - j for j in range(3)]
+            return [raw[j][0] for j in idx], [raw[j][1] for j in idx]
+
+        def raw_step(i):
+            (scans, poses), (nscans, nposes) = raw_window(i), raw_window(i + 1)
+            raw_runner.step_raw(scans, poses, FRAME_POINT_NUM, next_scans=nscans, next_poses=nposes)
+        for i in range(3):
+            raw_step(i)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for i in range(20):
+            raw_step(i)
+        torch.cuda.synchronize()
+        line["raw_scan_pipeline"] = {"value": round(20 / (time.perf_counter() - t1), 3), "unit": "scans/s",
+                                     "note": "H2D of 3 raw scans (5.8 MB) + device preprocessing (both on the side stream, one frame ahead) + the same step; "
+                                             "PCIe-inclusive, reported beside `value`, never as `value`"}
+    if world == 1 and args.streams > 1:
+        # configs[2]: S concurrent sequences advanced in lock step as one batch of 4*S samples
+        S = args.streams
+        ms = streaming.MultiStreamRunner(model, device, n_streams=S, vote=not args.no_vote, pipeline=not args.no_pipeline)
+        per_stream = [make_frames(4, seq_seed=100 + q) for q in range(S)]
+        batched = []
+        for f in range(4):
+            devs = [runner.upload(per_stream[q][f][0], per_stream[q][f][1]) for q in range(S)]
+            batched.append((ms.batch_inputs(devs), [per_stream[q][f][2] for q in range(S)]))
+        def ms_step(i):
+            nxt = batched[(i + 1) % 4][0] if ms.pipeline else None      # the next batch's encoder beside this batch's decoder
+            return ms.step(*batched[i % 4], next_batched=nxt)
+        for i in range(3):
+            ms_step(i)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        n_it = 10
+        for i in range(n_it):
+            ms_step(3 + i)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t2
+        line["batched_streams"] = {"streams": S, "value": round(S * n_it / dt, 3), "unit": "scans/s",
+                                   "ms_per_batched_step": round(1e3 * dt / n_it, 3),
+                                   "hbm_allocated_gb": round(torch.cuda.max_memory_allocated(device) / 1e9, 2),
+                                   "note": "BASELINE configs[2]; reported beside `value`, never as `value`"}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, out):
+    """--dump-outputs: what StreamRunner.step handed back for the last timed step -- every tensor of its result (TTA logits
+    `pred_cls`, TTA labels of the padded scan, labels of the raw scan) and the voted frames (`voted_frame_ids`, their refined
+    labels concatenated as `voted_labels`) -- as DIR/<name>.npy, float32 (labels are small integers: exact) or float64.  About
+    9 MiB at the bench's shape; the whole set must stay within 64 MiB."""
+    arrays = {k: v for k, v in out.items() if torch.is_tensor(v)}
+    voted = out.get("voted", [])
+    arrays["voted_frame_ids"] = torch.tensor([fid for fid, _ in voted], dtype=torch.float64)
+    arrays["voted_labels"] = torch.cat([lab.reshape(-1) for _, lab in voted]) if voted else torch.zeros(0)
+    arrays = {k: v.detach().cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -761,28 +876,42 @@ def main():
                     help="do not overlap the encoder of frame t+1 with the decoder of frame t")
     ap.add_argument("--no-raw", action="store_true", help="skip the PCIe-inclusive raw-scan leg (profiling runs: keeps the trace to "
                                                          "the headline step)")
-    ap.add_argument("--cpu-scans", type=int, default=4, help="timed scans of the CPU baseline (0 = skip); 4 scans = about 15 s")
+    ap.add_argument("--cpu-scans", type=int, default=None,
+                    help="with --full: timed scans of the CPU baseline (0 = skip; default 4 = about 15 s)")
     ap.add_argument("--streams", type=int, default=0,
-                    help="also time S concurrent sequences batched on the GPU (BASELINE configs[2]); reported beside value")
+                    help="with --full: also time S concurrent sequences batched on the GPU (BASELINE configs[2]); reported beside value")
     ap.add_argument("--train-steps", type=int, default=None,
-                    help="timed stage-2 DDP training steps on all ranks (BASELINE configs[4]; 0 = skip; default 3, 0 with "
-                         "--dry-launch); reported beside value")
+                    help="with --full or --dry-launch: timed stage-2 DDP training steps on all ranks (BASELINE configs[4]; 0 = skip; "
+                         "default 3 with --full, 0 with --dry-launch); reported beside value")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: instrumented look steps, the dominant kernel's roofline, the "
+                         "raw-scan pipeline, --streams, the stage-2 training step and the CPU baseline.  Without it a run sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed (rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--no-skip-padding", action="store_true",
                     help="compute the point head on the padding tail of every scan too (A/B; the runner's default leaves those "
                          "logits at zero: val_StreamMOS.py:113 cuts them off)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="only rehearse the rank launch: gloo ranks join the group, time a barrier, rank 0 prints n_gpus")
     ap.add_argument("--label-log", default=None,
-                    help="write the launch-ordered list of kernel labels of one step to this JSON file (used by "
+                    help="with --full: write the launch-ordered list of kernel labels of one step to this JSON file (used by "
                          "profiles/pmc_summary.py to tell the conv launches of a rocprofv3 --pmc pass apart; needs --no-pipeline)")
     args = ap.parse_args()
+    if not (args.full or args.dry_launch):
+        asked = [flag for flag, on in (("--cpu-scans", args.cpu_scans), ("--train-steps", args.train_steps),
+                                       ("--streams", args.streams > 1), ("--label-log", args.label_log)) if on]
+        if asked:
+            ap.error("%s: measured only with --full" % ", ".join(asked))
 
     from streammos_amd import launch
     if args.gpus > 1 and not launch.under_launcher():
         # no launcher around us: become the launcher.  Nothing above this line touches the GPU (importing torch does not).
         sys.exit(launch.self_launch(args.gpus, sys.argv[1:], script=os.path.abspath(__file__)))
     if args.train_steps is None:
-        args.train_steps = 0 if args.dry_launch else 3
+        args.train_steps = 3 if args.full and not args.dry_launch else 0
+    if args.cpu_scans is None:
+        args.cpu_scans = 4 if args.full else 0
     if args.dry_launch:
         return dry_launch(args)
 
@@ -832,21 +961,23 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # first a few steps with HIP-event brackets around every labelled launch (reported as hip_kernel_ms_per_step_warmup).  The TIMED region
-    # carries no instrumentation at all -- brackets around the 36 launches of the dominant family cost 0.3 ms of host time per
-    # step and 3 % of `value` when they were tried; the roofline's kernel is chosen and timed afterwards, in serial steady-state
-    # steps (family_roofline).
+    # --full: first a few steps with HIP-event brackets around every labelled launch (reported as hip_kernel_ms_per_step_warmup).
+    # The TIMED region carries no instrumentation at all -- brackets around the 36 launches of the dominant family cost 0.3 ms of
+    # host time per step and 3 % of `value` when they were tried; the roofline's kernel is chosen and timed afterwards, in serial
+    # steady-state steps (family_roofline).
     n_look = min(max(args.warmup, 1), 5)
-    with profiling.kernel_timer() as kt:
-        for i in range(n_look):               # extra, instrumented steps: a look at the launches, not part of W
-            one_step(i)
-    warm = kt.summary()
+    warm = None
+    if args.full:
+        with profiling.kernel_timer() as kt:
+            for i in range(n_look):               # extra, instrumented steps: a look at the launches, not part of W
+                one_step(i)
+        warm = kt.summary()
     # the W untimed warm-up steps proper, exactly as the timed ones (no instrumentation): the timed region then starts on a GPU
     # that has been busy up to the synchronize in front of it (reading the brackets back leaves it idle for milliseconds)
     for i in range(args.warmup):
         one_step(i)
 
-    if args.label_log and rank == 0:
+    if args.full and args.label_log and rank == 0:
         with profiling.kernel_timer() as kt_seq:
             one_step(args.warmup)
         torch.cuda.synchronize()
@@ -856,10 +987,11 @@ def main():
     t0 = time.perf_counter()
     half = args.steps // 2
     e_mid, e_end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    out = None
     for i in range(args.steps):
         if i == half:
             e_mid.record()                 # on the runner's main stream, behind step `half - 1`
-        one_step(args.warmup + i)
+        out = one_step(args.warmup + i)
     e_end.record()
     enqueue = time.perf_counter() - t0     # host time to issue all steps (the GPU may still be running)
     sync()
@@ -877,24 +1009,9 @@ def main():
     line = None
     if rank == 0:
         value = world * args.steps / elapsed
-        eng = getattr(model, "_engine", None)
-        ctx, stem_class_rows = {}, (0, 0, 0, 0)
-        if eng is not None and eng.sparse_stem and eng.stem_w is not None:
-            # occupancy of the frames the timed region cycled through (device-side counts of the stem plan, read here,
-            # outside the timed region): rows per launch of the compact scatter target / the sparse first stage
-            from streammos_amd import ops as _ops
-            metas = [_ops.stem_plan(d["pcds_coord"], *eng.bev_hw).meta.cpu().numpy() for d, _ in dev_frames]
-            stem_class_rows = tuple(float(np.mean([m[8 + c] - m[4 + c] for m in metas])) for c in range(4))
-            ctx["stem_rows"] = float(np.mean([m[11] for m in metas]))
-            ctx["stem_class_rows"] = stem_class_rows
+        ctx = {}
         if not args.no_skip_padding:
             ctx["live_fraction"] = float(np.mean([d["n_valid"] for d, _ in dev_frames])) / FRAME_POINT_NUM
-        roof, families = family_roofline(model, device, dev_frames, args, ctx, one_step)
-        exec_tflop = None
-        if eng is not None and eng.layout == "cl":
-            d0 = dev_frames[0][0]
-            bs, t, _, n = d0["pcds_xyzi"].shape[:4]
-            exec_tflop = executed_flops(eng, bs, n, t, stem_class_rows, ctx.get("live_fraction", 1.0)) / 1e12
         line = {
             "metric": "LiDAR scans/sec (StreamMOS streaming inference + voxel voting)",
             "value": round(value, 3), "unit": "scans/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -906,76 +1023,17 @@ def main():
                        "tta": 4, "frame_point_num": FRAME_POINT_NUM, "parallelism": "sequence-shard x%d" % world,
                        "real_points_per_scan": round(float(np.mean([d["n_valid"] for d, _ in dev_frames]))),
                        "padding_tail": "point head skipped (logits zero)" if not args.no_skip_padding else "computed"},
-            "roofline": roof,
             "path_roofline": {"bound": "hbm", "achieved": round(value / world * ALG_GB_PER_SCAN, 1), "peak": HBM_PEAK_GBS,
                               "unit": "GB/s", "frac": round(value / world * ALG_GB_PER_SCAN / HBM_PEAK_GBS, 4),
                               "note": "scans/s/GPU x 11.2 GB algorithmic bytes per scan (SURVEY.md 8d)"},
-            "path_compute_roofline": (None if exec_tflop is None else
-                                      {"bound": "mfma", "achieved": round(value / world * exec_tflop, 1),
-                                       "peak": FP32_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                       "frac": round(value / world * exec_tflop / FP32_PEAK_TFLOPS, 4),
-                                       "executed_tflop_per_scan": round(exec_tflop, 4),
-                                       "dense_equivalent_tflops": round(value / world * ALG_TFLOP_PER_SCAN, 1),
-                                       "note": "scans/s/GPU x the FLOPs the engine really executes per scan (bench.executed_flops "
-                                               "walks the engine's layers and the frames' occupancy) against the fp32 MFMA = "
-                                               "vector peak; dense_equivalent = the reference's 0.53 TFLOP/scan x scans/s, kept for "
-                                               "comparison only (the sparse first stage and the restructured conv_1 skip work)"}),
             "host_enqueue_ms_per_step": round(1e3 * enqueue / args.steps, 3),
             "second_half_ms_per_step": None if second_half_ms is None else round(second_half_ms, 3),
-            "stem_rows_per_launch": None if ctx.get("stem_rows") is None else round(ctx["stem_rows"]),
-            "stem_class_rows": [round(r) for r in stem_class_rows],
             "live_fraction": None if ctx.get("live_fraction") is None else round(ctx["live_fraction"], 4),
-            "kernel_families_serial": families,
-            "hip_kernel_ms_per_step_warmup": {k: round(v[1] / n_look, 4) for k, v in sorted(warm.items())},
         }
-        if world == 1 and not args.no_raw:
-            # PCIe-inclusive variant (never `value`): raw scans uploaded every step, preprocessing on the device
-            raw_runner = streaming.StreamRunner(model, device, vote=not args.no_vote, pipeline=not args.no_pipeline,
-                                                skip_padding=not args.no_skip_padding)
-            from streammos_amd import synth as _synth
-            raw = [(_synth.synthetic_scan(k), _synth.synthetic_pose(k)) for k in range(6)]
-            def raw_window(i):
-                idx = [(i + 2) % 4 + 2 - j for j in range(3)]
-                return [raw[j][0] for j in idx], [raw[j][1] for j in idx]
-
-            def raw_step(i):
-                (scans, poses), (nscans, nposes) = raw_window(i), raw_window(i + 1)
-                raw_runner.step_raw(scans, poses, FRAME_POINT_NUM, next_scans=nscans, next_poses=nposes)
-            for i in range(3):
-                raw_step(i)
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            for i in range(20):
-                raw_step(i)
-            torch.cuda.synchronize()
-            line["raw_scan_pipeline"] = {"value": round(20 / (time.perf_counter() - t1), 3), "unit": "scans/s",
-                                         "note": "H2D of 3 raw scans (5.8 MB) + device preprocessing (both on the side stream, one frame ahead) + the same step; "
-                                                 "PCIe-inclusive, reported beside `value`, never as `value`"}
-        if world == 1 and args.streams > 1:
-            # configs[2]: S concurrent sequences advanced in lock step as one batch of 4*S samples
-            S = args.streams
-            ms = streaming.MultiStreamRunner(model, device, n_streams=S, vote=not args.no_vote, pipeline=not args.no_pipeline)
-            per_stream = [make_frames(4, seq_seed=100 + q) for q in range(S)]
-            batched = []
-            for f in range(4):
-                devs = [runner.upload(per_stream[q][f][0], per_stream[q][f][1]) for q in range(S)]
-                batched.append((ms.batch_inputs(devs), [per_stream[q][f][2] for q in range(S)]))
-            def ms_step(i):
-                nxt = batched[(i + 1) % 4][0] if ms.pipeline else None      # the next batch's encoder beside this batch's decoder
-                return ms.step(*batched[i % 4], next_batched=nxt)
-            for i in range(3):
-                ms_step(i)
-            torch.cuda.synchronize()
-            t2 = time.perf_counter()
-            n_it = 10
-            for i in range(n_it):
-                ms_step(3 + i)
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t2
-            line["batched_streams"] = {"streams": S, "value": round(S * n_it / dt, 3), "unit": "scans/s",
-                                       "ms_per_batched_step": round(1e3 * dt / n_it, 3),
-                                       "hbm_allocated_gb": round(torch.cuda.max_memory_allocated(device) / 1e9, 2),
-                                       "note": "BASELINE configs[2]; reported beside `value`, never as `value`"}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out)
+        if args.full:
+            side_measurements(line, args, model, runner, device, dev_frames, ctx, one_step, warm, n_look, value, world)
 
     if args.train_steps > 0:
         # configs[4]: every rank of the group trains (real DDP over RCCL when world > 1); rank 0 reports

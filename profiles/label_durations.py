@@ -1,7 +1,7 @@
 """Per-LABEL kernel durations of one steady-state step (the kernel-stats CSVs aggregate by kernel
 template, so the bench line's dominant label could not be read off them).
 
-    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 bench.py --steps 20 --warmup 6 --cpu-scans 0 --no-raw \
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python3 bench.py --full --steps 20 --warmup 6 --cpu-scans 0 --no-raw \
         --no-pipeline --label-log labels.json            (one stream: dispatch order = launch order)
     python profiles/label_durations.py <kernel_trace.csv> labels.json [bench_line.json] > profiles/rNN_label_durations.csv
 

@@ -1,6 +1,6 @@
 """MFMA-busy per kernel from one rocprofv3 --pmc pass (SQ_VALU_MFMA_BUSY_CYCLES, GRBM_GUI_ACTIVE) over bench.py.
 
-    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d <dir> -- python3 bench.py --steps 3 --warmup 2 --frames 3 --cpu-scans 0 --no-pipeline
+    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d <dir> -- python3 bench.py --full --steps 3 --warmup 2 --frames 3 --cpu-scans 0 --no-pipeline
     python profiles/mfma_busy_summary.py <counter_collection.csv>
 
 SQ_VALU_MFMA_BUSY_CYCLES counts cycles summed over all SIMDs; GRBM_GUI_ACTIVE is summed over the 8 XCDs

@@ -1,6 +1,6 @@
 """HBM traffic per launch of the hand-written point kernels from two rocprofv3 --pmc passes.
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <fetch_dir> -- python3 bench.py --steps 3 --warmup 2 --frames 3 --cpu-scans 0 --no-pipeline --label-log labels.json
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <fetch_dir> -- python3 bench.py --full --steps 3 --warmup 2 --frames 3 --cpu-scans 0 --no-pipeline --label-log labels.json
     rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d <write_dir> -- python3 bench.py ... (same)
     python profiles/pmc_summary.py <fetch_counter_collection.csv> <write_counter_collection.csv> labels.json > profiles/pmc_traffic.json
 

@@ -13,7 +13,7 @@ import sys
 import numpy as np
 import pytest
 
-from streammos_amd import kitti, synth
+from streammos_amd import kitti, streaming, synth
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,6 +35,38 @@ def test_bench_gpus_2_spawns_two_ranks_on_the_device():
     print("2 ranks on one device: %.1f scans/s aggregate, %.2f ms/step" % (line["value"], line["ms_per_step"]))
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["config"]["parallelism"] == "sequence-shard x2"
     assert line["steps"] == 3 and line["value"] > 0 and abs(line["value"] - 2 * 3 / (line["ms_per_step"] * 3e-3)) < 0.01 * line["value"]
+
+
+def test_bench_plain_run_reports_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline line only (none of the side measurements),
+    and DIR holds what the last timed step returned -- the TTA logits, their TTA labels, the raw scan's labels and, at frame 7,
+    the eight frames the voting window refines at once -- in float32 / float64, 64 MiB at most."""
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "4", "--frames", "3",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=900, env=_env())
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    line = lines[0]
+    assert line["steps"] == 4 and line["n_gpus"] == 1 and line["unit"] == "scans/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert abs(line["value"] - 1e3 / line["ms_per_step"]) < 0.01 * line["value"]
+    for side in ("roofline", "kernel_families_serial", "raw_scan_pipeline", "batched_streams", "stage2_training", "cpu_baseline"):
+        assert side not in line, side
+    got = {p.stem: np.load(p) for p in dump.glob("*.npy")}
+    assert sorted(got) == ["labels", "pred_cls", "raw_labels", "voted_frame_ids", "voted_labels"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    logits, labels = got["pred_cls"], got["labels"]
+    assert logits.shape[:3] == (4, 3, 160000) and labels.shape == (160000,) and np.isfinite(logits).all()
+    live = np.abs(logits).reshape(4 * 3, -1).max(0) > 0          # the padding tail's logits are left at zero
+    assert 0 < live.sum() < live.size
+    tta = np.exp(logits - logits.max(1, keepdims=True))
+    tta = (tta / tta.sum(1, keepdims=True)).mean(0).argmax(0).reshape(-1)
+    assert (tta[live] == labels[live]).mean() >= 0.9999
+    assert set(np.unique(got["raw_labels"])) <= {0.0, 1.0, 2.0}
+    assert got["voted_frame_ids"].tolist() == list(range(8)) and got["voted_labels"].size > 8 * 1000
+    assert set(np.unique(got["voted_labels"])) <= set(float(v) for v in streaming.LEARNING_MAP_INV.values())
 
 
 def _write_sequence(seq, n, first):
@@ -72,7 +104,7 @@ def test_run_sequence_gpus_2_shards_whole_sequences(tmp_path):
 
 
 def test_bench_gpus_2_trains_stage2_as_ddp_and_reproduces_the_pinned_loss(tmp_path, golden):
-    """`bench.py --gpus 2 --train-steps 1`: after the inference timing BOTH ranks run the stage-2 step as real DDP on the group
+    """`bench.py --gpus 2 --full --train-steps 1`: after the inference timing BOTH ranks run the stage-2 step as real DDP on the group
     they already form (train_StreamMOS_seg.py:130,143,176-177), rank 0 reports `stage2_training` with the group's size, and an
     N > 1 line also carries `roofline` and `cpu_baseline`.  Fed the batch of tests/golden/training.npz (written by the
     reference) in the mode that fixture pins stage 2 in (eval), every rank must reproduce the reference's loss, and the
@@ -84,7 +116,7 @@ def test_bench_gpus_2_trains_stage2_as_ddp_and_reproduces_the_pinned_loss(tmp_pa
     np.savez(tmp_path / "batch.npz", **nb)
     env = dict(_env(), SMOS_BENCH_TRAIN_BATCH=str(tmp_path / "batch.npz"), SMOS_BENCH_TRAIN_EVAL="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "3",
-                          "--cpu-scans", "1", "--no-raw", "--train-steps", "1"], capture_output=True, text=True, timeout=1200, env=env)
+                          "--full", "--cpu-scans", "1", "--no-raw", "--train-steps", "1"], capture_output=True, text=True, timeout=1200, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -111,7 +143,7 @@ def test_bench_gpus_2_train_mode_counts_syncbn_collectives_on_the_wire():
     all_gather per layer and forward, counted where torch.distributed issues it), both ranks finish with a finite loss."""
     env = dict(_env(), SMOS_BENCH_TRAIN_POINTS="4096", SMOS_BENCH_TRAIN_BATCH_PER_GPU="1")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "3",
-                          "--cpu-scans", "0", "--no-raw", "--train-steps", "1"], capture_output=True, text=True, timeout=1200, env=env)
+                          "--full", "--cpu-scans", "0", "--no-raw", "--train-steps", "1"], capture_output=True, text=True, timeout=1200, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     tr = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")][-1]["stage2_training"]
     assert "error" not in tr, tr

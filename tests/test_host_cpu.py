@@ -242,6 +242,15 @@ def test_bench_gpus_flag_starts_its_own_ranks():
     assert one.returncode == 0 and json.loads(one.stdout.strip().splitlines()[-1])["n_gpus"] == 1
 
 
+def test_bench_side_measurements_need_full():
+    """A plain bench run measures the headline only: asking for a side measurement without --full is refused at argument
+    parsing (before any rank is started or the GPU is touched) instead of being dropped silently."""
+    for extra in (["--train-steps", "1"], ["--cpu-scans", "2"], ["--streams", "8"], ["--label-log", "labels.json"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + extra,
+                             capture_output=True, text=True, timeout=300)
+        assert out.returncode == 2 and "only with --full" in out.stderr and extra[0] in out.stderr, (extra, out.stderr[-2000:])
+
+
 def test_bench_gpus_2_dry_launch_trains_stage2_on_both_ranks():
     """`bench.py --gpus 2 --dry-launch --train-steps 1`: the ranks the program started itself form one group and run the
     stage-2 DDP step through bench.train_bench (CPU tensors over gloo at the rehearsal shape); rank 0 reports the size of the
