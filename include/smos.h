@@ -513,6 +513,17 @@ int smos_gather_scatter_cl_view(const float* grid, int64_t grid_pitch, const flo
                                 int64_t Hg, int64_t Wg, int64_t N, int64_t Ho, int64_t Wo, const int32_t* n_live,
                                 smos_stream_t stream);
 
+/* Per-frame label outputs of the overlapped sequence loop (streammos_amd/run_sequence.py).  labels [n] uint8 in {0,1,2}
+ * (4-byte aligned) -> words [n] int32 (16-byte aligned; NULL: not written): lut != 0 the learning_map_inv value 0 / 9 / 251
+ * (predictions/), lut == 0 the label itself (predictions_bf/).  gt [n] uint32 (16-byte aligned; NULL: nothing counted) holds
+ * SemanticKITTI label words, mapped through gt_map[word & 0xFFFF] (map_n int32 entries; ids >= map_n count as 0); counts[6]
+ * (device uint64) += tp1, tp2, pred1, pred2, gt1, gt2 over the points whose mapped gt is not 0 (kitti.MovingIoU.add). */
+int smos_label_words(const uint8_t* labels, int64_t n, int32_t lut, int32_t* words, const uint32_t* gt, const int32_t* gt_map,
+                     int32_t map_n, uint64_t* counts, smos_stream_t stream);
+/* The same for voted LUT words (int32 [n], 16-byte aligned): class 2 for 251, 1 for 9, 0 otherwise; words gets a copy. */
+int smos_label_count_voted(const int32_t* voted, int64_t n, int32_t* words, const uint32_t* gt, const int32_t* gt_map,
+                           int32_t map_n, uint64_t* counts, smos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

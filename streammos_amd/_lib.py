@@ -85,6 +85,8 @@ SIGNATURES = {
     "smos_gather_scatter_cl_view": [vp, i64, vp, i32, i64, c_f32p, vp, i32, i64, c_f32p, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp],
     "smos_gather_scatter_cl_live": [vp, i64, vp, i32, c_f32p, vp, i32, c_f32p, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp],
     "smos_upsample_concat": [ctypes.POINTER(vp), c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, i32, vp, i64, i64, i64, vp],
+    "smos_label_words": [vp, i64, i32, vp, vp, vp, i32, vp, vp],
+    "smos_label_count_voted": [vp, i64, vp, vp, vp, i32, vp, vp],
 }
 
 _lib = None

@@ -11,6 +11,15 @@ import torch
 from . import _lib, preprocess
 
 
+def check_in_range_counts(counts, frame_point_num):
+    """Host copy of a window's ``in_range_counts`` -> the host path's error (preprocess.pad_scan) for a scan that leaves no
+    padding."""
+    for t, c in enumerate(counts):
+        if c >= frame_point_num:
+            raise ValueError("scan %d of the window has %d in-range points, frame_point_num=%d leaves no padding "
+                             "(the reference asserts pad_length > 0)" % (t, c, frame_point_num))
+
+
 class DevicePreprocessor:
     def __init__(self, device, spec=None, frame_point_num=160000, tta=True):
         self.device = torch.device(device)
@@ -75,11 +84,7 @@ class DevicePreprocessor:
 
     def check_capacity(self, built):
         """Raises like preprocess.pad_scan when a scan of `built` left no padding (synchronises the stream)."""
-        counts = built["in_range_counts"].cpu().tolist()
-        for t, c in enumerate(counts):
-            if c >= self.N:
-                raise ValueError("scan %d of the window has %d in-range points, frame_point_num=%d leaves no padding "
-                                 "(the reference asserts pad_length > 0)" % (t, c, self.N))
+        check_in_range_counts(built["in_range_counts"].cpu().tolist(), self.N)
 
     def unpad_labels(self, labels, built):
         """labels [N] uint8 of the padded sample -> [n_raw] uint8 for the raw scan (0 where out of range)."""

@@ -335,6 +335,62 @@ def box_vote(points, labels, boxes, counts, pose_diff=None):
     return counts
 
 
+def _label_args(name, words, gt, gt_map, counts, n, device):
+    """Checks shared by label_words / voted_label_counts; returns the raw pointers (None where absent)."""
+    _require_cuda(name, words, gt, gt_map, counts)
+    if words is not None and (words.dtype != torch.int32 or not words.is_contiguous() or words.numel() < n
+                              or words.data_ptr() % 16 or words.device != device):
+        raise RuntimeError("%s: words must be a contiguous, 16-byte aligned int32 tensor of >= n elements on the labels' device" % name)
+    if gt is None:
+        return (words.data_ptr() if words is not None else None), None, None, 0, None
+    if gt_map is None or counts is None:
+        raise RuntimeError("%s: counting needs gt_map and counts" % name)
+    if gt.dtype not in (torch.int32, torch.uint32) or not gt.is_contiguous() or gt.numel() != n or gt.data_ptr() % 16:
+        raise RuntimeError("%s: gt must be a contiguous, 16-byte aligned 32-bit tensor with one word per label" % name)
+    if gt_map.dtype != torch.int32 or not gt_map.is_contiguous() or gt_map.dim() != 1:
+        raise RuntimeError("%s: gt_map must be a contiguous int32 vector" % name)
+    if counts.dtype not in (torch.int64, torch.uint64) or not counts.is_contiguous() or counts.numel() != 6:
+        raise RuntimeError("%s: counts must be a contiguous 64-bit tensor of 6 counters" % name)
+    if not (gt.device == gt_map.device == counts.device == device):
+        raise RuntimeError("%s: every tensor must be on the labels' device" % name)
+    return (words.data_ptr() if words is not None else None), gt.data_ptr(), gt_map.data_ptr(), gt_map.numel(), counts.data_ptr()
+
+
+def label_words(labels, words=None, lut=True, gt=None, gt_map=None, counts=None):
+    """One frame's prediction words and moving-IoU counts in one launch (csrc/labels.hip).  labels [n] uint8 in {0,1,2};
+    words [>=n] int32 (allocated when None) gets the learning_map_inv value 0 / 9 / 251 per point (lut=True, predictions/)
+    or the label itself (lut=False, predictions_bf/).  With gt ([n] 32-bit SemanticKITTI label words), gt_map
+    (kitti.learning_map_lut() as int32 on the device) and counts ([6] int64): counts += tp[1:3], pred[1:3], gt[1:3] of
+    kitti.MovingIoU.add(gt_map[gt & 0xFFFF], labels).  Returns words."""
+    _require_cuda("label_words", labels)
+    if labels.dtype != torch.uint8 or labels.dim() != 1 or not labels.is_contiguous() or labels.data_ptr() % 4:
+        raise RuntimeError("label_words: labels must be a contiguous, 4-byte aligned uint8 vector")
+    n = labels.shape[0]
+    if words is None:
+        words = torch.empty(n, dtype=torch.int32, device=labels.device)
+    w, g, gm, mn, c = _label_args("label_words", words, gt, gt_map, counts, n, labels.device)
+    lib = _lib.load()
+    with _on(labels.device):
+        rc = lib.smos_label_words(labels.data_ptr(), n, 1 if lut else 0, w, g, gm, mn, c, _stream(labels))
+    _lib.check(rc, "smos_label_words")
+    return words
+
+
+def voted_label_counts(voted, gt, gt_map, counts, words=None):
+    """The same for a voted frame: voted [n] int32 LUT words (vote_resolve with the LUT) count as class 2 for 251, 1 for 9,
+    0 otherwise (run_sequence's refined IoU); words (optional, [>=n] int32) gets a copy of them."""
+    _require_cuda("voted_label_counts", voted)
+    if voted.dtype != torch.int32 or voted.dim() != 1 or not voted.is_contiguous() or voted.data_ptr() % 16:
+        raise RuntimeError("voted_label_counts: voted must be a contiguous, 16-byte aligned int32 vector")
+    n = voted.shape[0]
+    w, g, gm, mn, c = _label_args("voted_label_counts", words, gt, gt_map, counts, n, voted.device)
+    lib = _lib.load()
+    with _on(voted.device):
+        rc = lib.smos_label_count_voted(voted.data_ptr(), n, w, g, gm, mn, c, _stream(voted))
+    _lib.check(rc, "smos_label_count_voted")
+    return words
+
+
 # ---------------------------------------------------------------------------------------------
 # fused encoder epilogues (inference engine)
 # ---------------------------------------------------------------------------------------------

@@ -41,14 +41,28 @@ def load_model(checkpoint=None, device="cuda:0", seg=False):
 def run_sequence(model, seq_dir, out_dir, device="cuda:0", vote=True, frame_point_num=160000, limit=None, seq_num=3,
                  device_preprocess=False):
     """device_preprocess=True: only the raw scans are uploaded (each once) and the validation preprocessing runs on
-    the GPU (identical to the host path except the last ulp of asinf / atan2f) -- the host then only
-    reads files and writes labels."""
+    the GPU (identical to the host path except the last ulp of asinf / atan2f) -- in the overlapped loop
+    of ``_run_overlapped``: file reads and label writes on threads of their own, nothing read back per frame.  The
+    default host-preprocessing loop is serial and reproduces the reference's numpy numerics to the last ulp."""
     spec = preprocess.VoxelSpec()
     files = sorted(f for f in os.listdir(os.path.join(seq_dir, "velodyne")) if f.endswith(".bin"))
     if limit:
         files = files[:limit]
     poses = kitti.read_poses(os.path.join(seq_dir, "poses.txt"), kitti.read_calibration(os.path.join(seq_dir, "calib.txt")))
     has_gt = os.path.isdir(os.path.join(seq_dir, "labels"))
+    res = {"sequence": os.path.basename(os.path.normpath(seq_dir)), "scans": len(files)}
+    if device_preprocess:
+        m_raw, m_ref = _run_overlapped(model, seq_dir, out_dir, files, poses, has_gt, device, vote, frame_point_num, seq_num)
+    else:
+        m_raw, m_ref = _run_serial(model, seq_dir, out_dir, files, poses, has_gt, device, vote, frame_point_num, seq_num, spec)
+    if has_gt:
+        res["network"] = m_raw.result()
+        if vote:
+            res["voted"] = m_ref.result()
+    return res
+
+
+def _run_serial(model, seq_dir, out_dir, files, poses, has_gt, device, vote, frame_point_num, seq_num, spec):
     runner = streaming.StreamRunner(model, device, vote=vote)
     m_raw, m_ref = kitti.MovingIoU(), kitti.MovingIoU()
     cache = {}
@@ -70,30 +84,11 @@ def run_sequence(model, seq_dir, out_dir, device="cuda:0", vote=True, frame_poin
             if has_gt:
                 m_ref.add(gt(fid), np.where(lab == 251, 2, np.where(lab == 9, 1, 0)))
 
-    dev_cache = {}
-
-    def dev_scan(i):
-        if i not in dev_cache:
-            dev_cache[i] = torch.from_numpy(np.ascontiguousarray(scan(i))).to(device, non_blocking=True)
-            for k in [k for k in dev_cache if k < i - 12]:
-                del dev_cache[k]
-        return dev_cache[i]
-
     for i in range(len(files)):
         idx = [min(j, len(files) - 1) for j in preprocess.window_indices(i, len(files), seq_num)]
-        if device_preprocess:
-            nxt = None
-            if i + 1 < len(files):
-                nxt = [min(j, len(files) - 1) for j in preprocess.window_indices(i + 1, len(files), seq_num)]
-            out = runner.step_raw([dev_scan(j) for j in idx], [poses[j] for j in idx], frame_point_num,
-                                  next_scans=[dev_scan(j) for j in nxt] if nxt else None,
-                                  next_poses=[poses[j] for j in nxt] if nxt else None)
-        else:
-            sample = preprocess.build_sample([scan(j) for j in idx], [poses[j] for j in idx], frame_point_num, spec, tta=True)
-            out = runner.step(runner.upload(sample, scan(i)), poses[i])
+        sample = preprocess.build_sample([scan(j) for j in idx], [poses[j] for j in idx], frame_point_num, spec, tta=True)
+        out = runner.step(runner.upload(sample, scan(i)), poses[i])
         raw = out["raw_labels"].cpu().numpy()
-        if device_preprocess:
-            runner.check_last_raw_sample()      # a scan that leaves no padding is an error, as on the host path
         kitti.write_prediction(os.path.join(out_dir, "predictions", files[i][:-4] + ".label"), labels_012=raw)
         if "bf_raw_labels" in out:          # val_StreamMOS_seg.py:141: raw 0/1/2 words, no LUT
             kitti.write_prediction(os.path.join(out_dir, "predictions_bf", files[i][:-4] + ".label"),
@@ -103,12 +98,138 @@ def run_sequence(model, seq_dir, out_dir, device="cuda:0", vote=True, frame_poin
         emit_refined(out["voted"])
     if runner.voter is not None:
         emit_refined(runner.voter.flush())
-    res = {"sequence": os.path.basename(os.path.normpath(seq_dir)), "scans": len(files)}
-    if has_gt:
-        res["network"] = m_raw.result()
-        if vote:
-            res["voted"] = m_ref.result()
-    return res
+    return m_raw, m_ref
+
+
+IN_FLIGHT = 4          # frames whose labels are on their way to the writer (output ring slots)
+READ_AHEAD = 6         # scans the reader thread may hold (input ring slots)
+
+
+def _iou_from_counts(counts):
+    """Device [6] int64 counters of ops.label_words (tp1, tp2, pred1, pred2, gt1, gt2) -> the kitti.MovingIoU they stand for."""
+    m = kitti.MovingIoU()
+    c = counts.cpu().numpy().astype(np.float64)
+    m.tp[:], m.pred[:], m.gt[:] = c[0:2], c[2:4], c[4:6]
+    return m
+
+
+def _run_overlapped(model, seq_dir, out_dir, files, poses, has_gt, device, vote, frame_point_num, seq_num):
+    """The device-preprocessing loop, overlapped (DESIGN.md "The sequence loop").  The reader thread reads scans and ground
+    truth into pinned slots; this thread uploads each once, runs StreamRunner(pipeline=True).step_raw with the next window,
+    and per frame only LAUNCHES the label kernel (prediction words + IoU counts, ops.label_words / voted_label_counts) into
+    the frame's device staging slot, copies the window's in-range counts there and queues one device-to-host copy of the
+    slot on a copy stream; the writer thread waits for that copy, checks the counts (the host path's capacity error) and
+    writes the files.  Nothing is read back per frame: the one wait is for a free output slot, IN_FLIGHT frames behind.
+    The IoU counters are read once, at the end.  Instance voting (vote="instance") still synchronises inside the voter
+    (ops.dbscan, the cluster tests of InstanceVoter.cluster_boxes)."""
+    from . import ops, sequence_io
+    from .device_preprocess import check_in_range_counts
+    device = torch.device(device)
+    n = len(files)
+    runner = streaming.StreamRunner(model, device, vote=vote, pipeline=True)
+    main = torch.cuda.current_stream(device)
+    copier = torch.cuda.Stream(device)
+    gt_map = torch.from_numpy(kitti.learning_map_lut()).to(device)
+    counts_raw = torch.zeros(6, dtype=torch.int64, device=device)
+    counts_ref = torch.zeros(6, dtype=torch.int64, device=device)
+    reader = sequence_io.ScanReader(seq_dir, files, ring=READ_AHEAD, labels=has_gt)
+    writer = None
+    try:
+        a4 = (reader.max_points + 3) // 4 * 4
+        cap = (2 + streaming.VOTE_WINDOW) * a4 + (seq_num + 3) // 4 * 4
+        dev_stage = [torch.empty(cap, dtype=torch.int32, device=device) for _ in range(IN_FLIGHT)]
+        host_stage = [torch.empty(cap, dtype=torch.int32, pin_memory=True) for _ in range(IN_FLIGHT)]
+        writer = sequence_io.SlotWriter(range(IN_FLIGHT))
+        dev_scans, gt_dev = {}, {}
+        pulled = [0]
+
+        def dev_scan(i):
+            while pulled[0] <= i:                     # frames arrive in order; each is uploaded once, from its pinned slot
+                fr = reader.get()
+                dev_scans[fr.index] = fr.scan.to(device, non_blocking=True)
+                if fr.label is not None:
+                    gt_dev[fr.index] = fr.label.to(device, non_blocking=True)
+                done = torch.cuda.Event(blocking=True)
+                done.record(main)
+                reader.release(fr, done)
+                pulled[0] += 1
+                for k in [k for k in dev_scans if k < fr.index - 12]:
+                    del dev_scans[k]
+            return dev_scans[i]
+
+        def launch_slot(frame, out, voted):
+            """Label kernels of one frame (frame None: the voter's flush) into a free slot, its D2H, the writer's job."""
+            k = writer.take()                         # back-pressure: waits while IN_FLIGHT slots are on their way
+            stage, off = dev_stage[k], 0
+            parts = {}
+
+            def section(name, m):
+                nonlocal off
+                parts[name] = (off, m)
+                off += (m + 3) // 4 * 4
+                return stage[parts[name][0]:parts[name][0] + m]
+
+            if frame is not None:
+                raw = out["raw_labels"]
+                ops.label_words(raw, words=section(("predictions", frame), raw.shape[0]), lut=True,
+                                gt=gt_dev.get(frame) if has_gt else None, gt_map=gt_map, counts=counts_raw)
+                if "bf_raw_labels" in out:
+                    ops.label_words(out["bf_raw_labels"], words=section(("predictions_bf", frame), raw.shape[0]), lut=False)
+                section("counts", seq_num).copy_(runner.last_in_range_counts())
+                if not vote:
+                    gt_dev.pop(frame, None)
+            if len(voted) > streaming.VOTE_WINDOW:
+                raise RuntimeError("run_sequence: the voter released %d frames at once (slots hold %d)"
+                                   % (len(voted), streaming.VOTE_WINDOW))
+            for fid, lab in voted:
+                ops.voted_label_counts(lab, gt_dev.pop(fid) if has_gt else None, gt_map, counts_ref,
+                                       words=section(("refined", fid), lab.shape[0]))
+            ready = torch.cuda.Event()
+            ready.record(main)
+            copier.wait_event(ready)
+            with torch.cuda.stream(copier):
+                host_stage[k][:off].copy_(stage[:off], non_blocking=True)
+            copied = torch.cuda.Event(blocking=True)
+            copied.record(copier)
+            host = host_stage[k].numpy()
+
+            def write():
+                if "counts" in parts:                 # the window's capacity check comes before any file of the frame
+                    o, m = parts["counts"]
+                    check_in_range_counts(host[o:o + m].tolist(), frame_point_num)
+                for key, (o, m) in parts.items():
+                    if key != "counts":
+                        sub, fid = key
+                        kitti.write_prediction(os.path.join(out_dir, sub, files[fid][:-4] + ".label"), lut_labels=host[o:o + m])
+
+            writer.submit(k, copied, write)
+
+        for i in range(n):
+            if writer.error is not None:
+                raise writer.error
+            idx = [min(j, n - 1) for j in preprocess.window_indices(i, n, seq_num)]
+            nxt = [min(j, n - 1) for j in preprocess.window_indices(i + 1, n, seq_num)] if i + 1 < n else None
+            out = runner.step_raw([dev_scan(j) for j in idx], [poses[j] for j in idx], frame_point_num,
+                                  next_scans=[dev_scan(j) for j in nxt] if nxt else None,
+                                  next_poses=[poses[j] for j in nxt] if nxt else None)
+            launch_slot(i, out, out["voted"])
+        if runner.voter is not None:
+            voted = runner.voter.flush()
+            if voted:
+                launch_slot(None, None, voted)
+        writer.close()                                # the files of every frame are written when this returns
+        if writer.error is not None:
+            raise writer.error
+        m_raw = _iou_from_counts(counts_raw) if has_gt else None
+        m_ref = _iou_from_counts(counts_ref) if has_gt and vote else None
+        return m_raw, m_ref
+    except BaseException:
+        if writer is not None:
+            writer.close()
+        torch.cuda.synchronize(device)                # nothing of this run stays in flight once the error is raised
+        raise
+    finally:
+        reader.close()
 
 
 def main():

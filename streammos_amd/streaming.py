@@ -444,6 +444,11 @@ class StreamRunner:
         if built is not None and getattr(self, "_pre", None) is not None:
             self._pre.check_capacity(built)
 
+    def last_in_range_counts(self):
+        """Device int32 [T]: the in-range point count of every scan of the last step_raw window (no synchronisation; a
+        count >= frame_point_num is the error check_last_raw_sample raises)."""
+        return self._last_built["in_range_counts"]
+
     def _pipelined(self, dev, next_dev):
         """Two HIP streams: encode(t+1) on the side stream while frame t is decoded on the main one.  (Putting the serial
         [third BEV stage -> temporal fusion] chain on a third stream of its own was measured too: 144 vs 146 scans/s, so
