@@ -302,6 +302,22 @@ int smos_conv_cl(const float* x, int64_t x_pitch, const float* wprep, const floa
                  float* out, int64_t out_pitch, int64_t B, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int32_t KH,
                  int32_t KW, int32_t stride, int32_t pad_h, int32_t pad_w, int32_t mt, int32_t act, float* chan_sums,
                  smos_stream_t stream);
+/* smos_conv_cl on the bf16 matrix cores (csrc/conv_bf16.hip; the engine's opt-in conv_precision "bf16"):
+ *   out = act(sum bf16(w) * bf16(x) + bias [+ res]);  products exact, sums / bias / residual / activation / chan_sums fp32.
+ * x is fp32 and rounded to bf16 (round-to-nearest-even) as the kernel stages it.  Same operands, pitches, alignment, act
+ * codes and chan_sums layout (smos_conv_cl_sum_chunks) as smos_conv_cl; Cin % 32 == 0, Cout % 32 == 0, Cout <= 2048,
+ * KH, KW <= 7, stride 1 or 2, explicit padding; the block shape is chosen inside.  Shapes whose staged input region does
+ * not fit are refused: ask smos_conv_bf16_cl_supported (1 / 0) first.
+ * wprep: Cout * Cin * KH * KW bf16 (uint16 bit patterns, rounded to nearest even) in MFMA operand order; with
+ * stage = ((cc * KH) + ky) * KW + kx (the 32-channel chunk outermost):
+ *   wprep[(((stage * (Cout / 32) + q) * 2 + s) * 64 + lane) * 8 + j]
+ *       = bf16(w[q * 32 + (lane & 31)][cc * 32 + 16 * s + 8 * (lane >> 5) + j][ky][kx]).
+ * Deterministic: bit-identical from run to run, whatever the grid, the stream or the batch size. */
+int smos_conv_bf16_cl_supported(int64_t Cin, int64_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t has_res);
+int smos_conv_bf16_cl(const float* x, int64_t x_pitch, const uint16_t* wprep, const float* bias, const float* res,
+                      int64_t res_pitch, float* out, int64_t out_pitch, int64_t B, int64_t H, int64_t W, int64_t Cin,
+                      int64_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad_h, int32_t pad_w, int32_t act,
+                      float* chan_sums, smos_stream_t stream);
 /* smos_conv_cl for the stride-1 3x3 "same" layers in the Winograd F(2x2, 3x3) form (csrc/conv_wino.hip): 4 instead of 9
  * multiply-adds per output and channel pair, arithmetic still plain fp32 -- the weights are transformed on the host in
  * float64 (U = G g G^T, rounded once), the input and output transforms are additions.  Replaces the same reference layers as

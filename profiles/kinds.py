@@ -2,6 +2,7 @@
 dispatches (stem_mark+scan = two kernels).  Shared by pmc_summary.py and label_durations.py."""
 KIND = (
     (("conv_igemm", "conv_rows", "conv_wino"), "conv_cl[", 1),
+    (("conv_bf16",), "conv_bf16[", 1),
     (("gather_scatter_cl",), "gather_scatter_cl[", 1),
     (("pointnet_scatter",), "pointnet_scatter[", 1),
     (("point_head",), "point_head[", 1),

@@ -50,6 +50,8 @@ SIGNATURES = {
     "smos_conv_cl_sum_chunks": [i64, i64],
     "smos_conv_cl": [vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "smos_conv_rows_cl": [vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp],
+    "smos_conv_bf16_cl_supported": [i64, i64, i32, i32, i32, i32],
+    "smos_conv_bf16_cl": [vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, vp, vp],
     "smos_conv_wino_sum_chunks": [i64, i64],
     "smos_conv_wino_cl": [vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i32, i32, vp, vp],
     "smos_basic_block_ws_floats": [i64, i64, i64, i64],

@@ -50,13 +50,27 @@ def _cl_w(w):
     return w.contiguous(memory_format=torch.channels_last)
 
 
+CONV_PRECISIONS = ("fp32", "bf16")
+
+
 class InferenceEngine:
-    def __init__(self, net, layout="cl"):
+    def __init__(self, net, layout="cl", conv_precision="fp32"):
         """layout "cl": every feature map channels-last (default; fastest under MIOpen's solver search and the natural
-        layout of the scatters and of the attention tokens); "nchw": the first version of the engine, kept for A/B."""
+        layout of the scatters and of the attention tokens); "nchw": the first version of the engine, kept for A/B.
+        conv_precision "fp32" (default: exact fp32 everywhere) or "bf16" (opt-in, channels-last only): every layer that goes
+        through _conv -- the BasicBlock, Unbalance and DownSample2D convs and the decoder's conv_1a / conv_2 -- runs on the
+        bf16 matrix-core kernel (csrc/conv_bf16.hip: bf16-rounded weights and activations, fp32 sums and epilogue); a layer
+        the kernel does not cover stays on the fp32 path and is counted (conv_precision_stats)."""
         if layout not in ("cl", "nchw"):
             raise ValueError("layout must be 'cl' or 'nchw'")
+        if conv_precision not in CONV_PRECISIONS:
+            raise ValueError("conv_precision must be one of %s, got %r" % (CONV_PRECISIONS, conv_precision))
+        if conv_precision != "fp32" and layout != "cl":
+            raise ValueError("conv_precision=%r needs layout='cl'" % (conv_precision,))
         self.layout = layout
+        self.conv_precision = conv_precision
+        self._bf16 = conv_precision == "bf16"
+        self._conv_route = {}           # bf16 mode: weight -> whether its last launch ran in bf16 (False: fp32 fallback)
         self.device = next(net.parameters()).device
         self.bev_hw = tuple(net.bev_wl_shape)
         enc = net.bev_net
@@ -176,6 +190,10 @@ class InferenceEngine:
         self.wino_chain = os.environ.get("SMOS_WINO_CHAIN", "0") == "1"   # EXPERIMENTAL: runs of BasicBlocks as one dataflow launch
         self._wprep = {}
         self._wino_plan = {}
+        if self._bf16:
+            # the block calls and the wino chain launch fp32 kernels: bf16 mode takes the launch-by-launch path
+            self.block_call = False
+            self.wino_chain = False
         self._shapes = None
         self._lsi = None
         self._hw = None
@@ -405,11 +423,29 @@ class InferenceEngine:
             return self._decode(enc, x2)
 
     # ---- channels-last path -----------------------------------------------------------------------
+    def conv_precision_stats(self):
+        """bf16 mode: {"bf16": layers whose last launch ran on the bf16 kernel, "fallback": layers that stayed on the fp32
+        path (shapes the bf16 kernel does not cover)}; one entry per layer, so after a step these are that step's counts.
+        fp32 mode: both 0."""
+        n16 = sum(1 for v in self._conv_route.values() if v)
+        return {"bf16": n16, "fallback": len(self._conv_route) - n16}
+
     def _conv(self, x, w, bias, act, stride=1, residual=None, out=None, chan_sums=None):
         """act(conv(x, w) + bias [+ residual]) for a folded weight w [Cout, Cin, KH, KW] ("same" padding for odd kernels)
         on channels-last maps: one launch of csrc/conv_igemm.hip; the operand-ordered copy of w is made once per (weight,
-        mt).  With SMOS_OWN_CONV=0: MIOpen conv + the separate bias / activation / residual pass."""
+        mt).  With SMOS_OWN_CONV=0: MIOpen conv + the separate bias / activation / residual pass.  conv_precision "bf16":
+        csrc/conv_bf16.hip where it covers the shape, else the fp32 path below (counted in conv_precision_stats)."""
         cout, cin, kh, kw = w.shape
+        if self._bf16:
+            ok = self.own_conv and ops.conv_bf16_ok(x, cout, (kh, kw), stride, residual, out, chan_sums)
+            self._conv_route[w.data_ptr()] = ok
+            if ok:
+                key = (w.data_ptr(), "bf16")          # never collides with the fp32 packings' keys
+                wp = self._wprep.get(key)
+                if wp is None:
+                    wp = self._wprep[key] = ops.conv_bf16_prepare(w)
+                return ops.conv_bf16_cl(x, wp, bias, act, cout, (kh, kw), stride=stride, residual=residual, out=out,
+                                        chan_sums=chan_sums)
         # fast accept (no per-launch predicate walk): channel counts the MFMA tiling covers and operands far below the 2 GiB of the
         # 32-bit buffer offsets (<= 2^26 input floats; a slice's pitch is at most twice its channels, Cout at most four times Cin)
         easy = (cin % 32 == 0 and cout % 32 == 0 and cout <= 4 * cin and kh <= 7 and kw <= 7 and (stride == 1 or stride == 2) and
@@ -508,9 +544,11 @@ class InferenceEngine:
             return self._conv(y, p.w2, p.b2, RELU, residual=x, out=out)
         bsz, c, h, w = y.shape
         if (self.own_conv and self.fused_gate_sums and c % 32 == 0 and c <= 256 and 1024 % c == 0 and
-                ops.conv_cl_supported(y, c, tuple(p.w2.shape[2:]))):
+                ops.conv_cl_supported(y, c, tuple(p.w2.shape[2:])) and
+                (not self._bf16 or ops.conv_bf16_ok(y, c, tuple(p.w2.shape[2:]), chan_sums=True))):
             # the conv's epilogue leaves the per-row-segment channel sums behind: no pass over y2 for the average pool
-            wino = self.wino and ops.conv_wino_ok(tuple(p.w2.shape[2:]), 1, c, c)
+            # (bf16 mode: the bf16 kernel writes them, in the table layout of conv_cl)
+            wino = not self._bf16 and self.wino and ops.conv_wino_ok(tuple(p.w2.shape[2:]), 1, c, c)
             chunks = ops.conv_wino_sum_chunks(h, w) if wino else ops.conv_sum_chunks(h, w)
             ws = self._block_ws(p, bsz * c * (chunks + 1))
             sums = ws[:bsz * chunks * c].view(bsz, chunks, c)

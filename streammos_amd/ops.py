@@ -704,6 +704,83 @@ def conv_cl(x, wprep, bias, act, cout, kernel, stride=1, padding=None, mt=1, res
     return out
 
 
+def conv_bf16_prepare(w):
+    """w [Cout, Cin, KH, KW] (BatchNorm folded, fp32) -> the bf16 weight block of smos_conv_bf16_cl (include/smos.h): rounded
+    once to nearest even (torch's .to(torch.bfloat16)), in MFMA operand order [cin chunk][ky][kx][Cout / 32][k-step][lane][8]
+    with lane = h * 32 + m holding w[32 q + m][32 chunk + 16 s + 8 h + j][ky][kx], j = 0..7."""
+    cout, cin, kh, kw = w.shape
+    if cin % 32 or cout % 32:
+        raise RuntimeError("conv_bf16_prepare: Cin %% 32 == 0 and Cout %% 32 == 0 required (got %s)" % (tuple(w.shape),))
+    #                q          m   chunk    s  h  j  ky  kx
+    v = w.detach().float().reshape(cout // 32, 32, cin // 32, 2, 2, 8, kh, kw)
+    v = v.permute(2, 6, 7, 0, 3, 4, 1, 5)           # -> [chunk, ky, kx, q, s, h, m, j]
+    return v.to(torch.bfloat16).reshape(-1).contiguous()
+
+
+_bf16_shape_ok = {}
+
+
+def conv_bf16_ok(x, cout, kernel, stride=1, residual=None, out=None, chan_sums=None):
+    """Shapes smos_conv_bf16_cl covers, as a predicate the engine asks before it routes a layer to it: the limits of
+    conv_cl_supported (channel multiples of 32, Cout <= 2048, kernel <= 7x7, stride 1 or 2, every operand below 2 GiB) plus a
+    block shape whose staged input region fits (smos_conv_bf16_cl_supported); channel sums never with a residual.
+    Shapes only: works on meta tensors."""
+    if chan_sums is not None and residual is not None:
+        return False
+    if not conv_cl_supported(x, cout, kernel, stride, residual, out):
+        return False
+    kh, kw = kernel
+    key = (x.shape[1], cout, kh, kw, stride, residual is not None)
+    ok = _bf16_shape_ok.get(key)
+    if ok is None:
+        ok = _bf16_shape_ok[key] = bool(_lib.load().smos_conv_bf16_cl_supported(*key[:5], int(key[5])))
+    return ok
+
+
+def conv_bf16_cl(x, wprep, bias, act, cout, kernel, stride=1, padding=None, residual=None, out=None, chan_sums=None):
+    """conv_cl with bf16 operands on the bf16 matrix cores (csrc/conv_bf16.hip): act(sum bf16(w) * bf16(x) + bias [+ residual])
+    with fp32 sums, bias, residual, activation and output.  wprep = conv_bf16_prepare(w); kernel = (KH, KW); padding defaults
+    to "same" for odd kernels; chan_sums: float32 [B, conv_sum_chunks(Ho, Wo), Cout] (the layout of conv_cl), not together
+    with a residual."""
+    _require_cuda("conv_bf16_cl", x, wprep, bias, residual, out, chan_sums)
+    b, cin, h, w = x.shape
+    kh, kw = kernel
+    ph, pw = padding if padding is not None else (kh // 2, kw // 2)
+    ho, wo = (h + 2 * ph - kh) // stride + 1, (w + 2 * pw - kw) // stride + 1
+    if wprep.dtype != torch.bfloat16 or wprep.numel() != cout * cin * kh * kw:
+        raise RuntimeError("conv_bf16_cl: weight block must hold %d bf16 (conv_bf16_prepare), got %d %s" %
+                           (cout * cin * kh * kw, wprep.numel(), wprep.dtype))
+    if x.dtype != torch.float32 or (bias is not None and (bias.dtype != torch.float32 or bias.numel() != cout)):
+        raise RuntimeError("conv_bf16_cl: x and bias must be float32 (bias of Cout entries)")
+    if out is None:
+        out = empty_cl(b, cout, ho, wo, x.device)
+    elif tuple(out.shape) != (b, cout, ho, wo) or out.dtype != torch.float32:
+        raise RuntimeError("conv_bf16_cl: out has shape %s, expected %s" % (tuple(out.shape), (b, cout, ho, wo)))
+    if residual is not None and (tuple(residual.shape) != (b, cout, ho, wo) or residual.dtype != torch.float32):
+        raise RuntimeError("conv_bf16_cl: residual has shape %s" % (tuple(residual.shape),))
+    if chan_sums is not None and (residual is not None or not chan_sums.is_contiguous() or chan_sums.dtype != torch.float32 or
+                                  tuple(chan_sums.shape) != (b, conv_sum_chunks(ho, wo), cout)):
+        raise RuntimeError("conv_bf16_cl: chan_sums must be contiguous float32 [B, conv_sum_chunks(Ho, Wo), Cout], without a residual")
+    lib = _lib.load()
+    label = ("conv_bf16[%dx%dx%dx%d->%dx%dx%dk%dx%d%s]" % (b, cin, h, w, cout, ho, wo, kh, kw, "+res" if residual is not None else "")
+             if profiling.enabled() else None)
+    args = (x.data_ptr(), _cl("conv_bf16_cl", x), wprep.data_ptr(), bias.data_ptr() if bias is not None else None,
+            residual.data_ptr() if residual is not None else None, _cl("conv_bf16_cl", residual) if residual is not None else 0,
+            out.data_ptr(), _cl("conv_bf16_cl", out), b, h, w, cin, cout, kh, kw, stride, ph, pw, int(act),
+            chan_sums.data_ptr() if chan_sums is not None else None)
+    with _on(x.device), profiling.span(label, "conv_bf16"):
+        rc = lib.smos_conv_bf16_cl(*args, _stream(x))
+    _lib.check(rc, "smos_conv_bf16_cl")
+    if label is not None and profiling._replay_label == label:
+        keep = (x, wprep, bias, residual, out, chan_sums)          # the closure keeps the operands alive
+
+        def again(keep=keep):
+            with _on(keep[0].device), profiling.span(label, "conv_bf16"):
+                _lib.check(lib.smos_conv_bf16_cl(*args, _stream(keep[0])), "smos_conv_bf16_cl")
+        profiling.offer_replay(label, again)
+    return out
+
+
 _WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
 
 

@@ -38,6 +38,7 @@ class AttNet(nn.Module):
         self.build_network()
         self.fast_inference = True      # eval-mode GPU inference runs the fused engine (streammos_amd/engine.py)
         self.engine_layout = "cl"       # "cl" (channels-last, default) or "nchw"
+        self.engine_conv_precision = "fp32"     # "fp32" (default, exact) or "bf16" (opt-in bf16 matrix-core convolutions)
         self.engine_miopen_search = True
         self._engine = None
 
@@ -80,9 +81,10 @@ class AttNet(nn.Module):
     def _engine_for(self, tensor):
         if not self.fast_inference or self.training or not tensor.is_cuda or torch.is_grad_enabled():
             return None
-        if self._engine is None or self._engine.device != tensor.device or self._engine.layout != self.engine_layout:
+        if (self._engine is None or self._engine.device != tensor.device or self._engine.layout != self.engine_layout or
+                self._engine.conv_precision != self.engine_conv_precision):
             from ... import engine
-            self._engine = engine.InferenceEngine(self, layout=self.engine_layout)
+            self._engine = engine.InferenceEngine(self, layout=self.engine_layout, conv_precision=self.engine_conv_precision)
         self._engine.miopen_search = self.engine_miopen_search
         if getattr(self, "engine_sparse_stem", None) is not None:
             self._engine.sparse_stem = bool(self.engine_sparse_stem)

@@ -39,11 +39,13 @@ def load_model(checkpoint=None, device="cuda:0", seg=False):
 
 
 def run_sequence(model, seq_dir, out_dir, device="cuda:0", vote=True, frame_point_num=160000, limit=None, seq_num=3,
-                 device_preprocess=False):
+                 device_preprocess=False, conv_precision=None):
     """device_preprocess=True: only the raw scans are uploaded (each once) and the validation preprocessing runs on
     the GPU (identical to the host path except the last ulp of asinf / atan2f) -- in the overlapped loop
     of ``_run_overlapped``: file reads and label writes on threads of their own, nothing read back per frame.  The
-    default host-preprocessing loop is serial and reproduces the reference's numpy numerics to the last ulp."""
+    default host-preprocessing loop is serial and reproduces the reference's numpy numerics to the last ulp.
+    conv_precision "fp32" / "bf16": the engine's convolution precision (streaming.set_conv_precision; None: the model's)."""
+    streaming.set_conv_precision(model, conv_precision)
     spec = preprocess.VoxelSpec()
     files = sorted(f for f in os.listdir(os.path.join(seq_dir, "velodyne")) if f.endswith(".bin"))
     if limit:
@@ -232,7 +234,7 @@ def _run_overlapped(model, seq_dir, out_dir, files, poses, has_gt, device, vote,
         reader.close()
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seq-dir", nargs="+", required=True)
     ap.add_argument("--out-dir", required=True)
@@ -249,6 +251,13 @@ def main():
     ap.add_argument("--frame-point-num", type=int, default=160000, help="Val.frame_point_num of config/StreamMOS.py:44")
     ap.add_argument("--device-preprocess", action="store_true",
                     help="range filter / pose alignment / TTA / quantisation on the GPU: only raw scans cross PCIe")
+    ap.add_argument("--conv-precision", choices=("fp32", "bf16"), default="fp32",
+                    help="convolutions of the engine in exact fp32 (default) or on the bf16 matrix cores (opt-in)")
+    return ap
+
+
+def main():
+    ap = build_parser()
     args = ap.parse_args()
     if args.gpus > 1 and not launch.under_launcher():
         import sys
@@ -266,7 +275,7 @@ def main():
     for d in mine:
         out = os.path.join(args.out_dir, os.path.basename(os.path.normpath(d))) if len(args.seq_dir) > 1 else args.out_dir
         res = run_sequence(model, d, out, device, vote=vote, limit=args.limit, frame_point_num=args.frame_point_num,
-                           device_preprocess=args.device_preprocess)
+                           device_preprocess=args.device_preprocess, conv_precision=args.conv_precision)
         print(json.dumps(dict(res, rank=rank, world=world)), flush=True)
 
 

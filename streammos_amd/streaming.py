@@ -212,18 +212,31 @@ def concurrent_stream(device, candidates=8, spin_cycles=400000):
     return best
 
 
+def set_conv_precision(model, conv_precision):
+    """model.engine_conv_precision = conv_precision ("fp32" / "bf16"; None leaves the model's setting).  The engine is
+    rebuilt on the next call when the value changes (AttNet._engine_for)."""
+    if conv_precision is None:
+        return
+    from .engine import CONV_PRECISIONS
+    if conv_precision not in CONV_PRECISIONS:
+        raise ValueError("conv_precision must be one of %s, got %r" % (CONV_PRECISIONS, conv_precision))
+    model.engine_conv_precision = conv_precision
+
+
 class StreamRunner:
     """infer -> TTA reduce -> labels for the raw scan -> voxel voting, all on one device, one stream."""
 
     def __init__(self, model, device="cuda:0", vote=True, recip_quantize=False, graph=False, split=1, pipeline=False,
-                 skip_padding=True):
+                 skip_padding=True, conv_precision=None):
         """graph=True captures the network forward of a frame into hipGraphs (first frame: learned memory embedding;
         later frames: recurrent memory) that are replayed on static buffers -- one launch per scan instead of ~180.
         split=k additionally cuts the TTA batch into k independent groups (TTA variants never interact inside the
         network) whose graphs are replayed on k HIP streams at once, so that the many small kernels of one group fill
-        the CUs the other group leaves idle.  Voting stays outside the graphs (pose matrices are launch arguments)."""
+        the CUs the other group leaves idle.  Voting stays outside the graphs (pose matrices are launch arguments).
+        conv_precision "fp32" / "bf16": sets model.engine_conv_precision (None: the model's setting, "fp32" by default)."""
         self.device = torch.device(device)
         self.model = model.to(self.device).eval()
+        set_conv_precision(self.model, conv_precision)
         # vote: False / True (voxel voting) / "instance" (voxel + instance voting; needs the StreamMOS_seg model)
         if vote == "instance":
             self.voter = InstanceVoter(self.device, recip_quantize=recip_quantize)
@@ -550,12 +563,13 @@ class MultiStreamRunner:
     concurrent sequences on one GPU, every stream's recurrent memory and voting window resident in HBM).
     Streams never interact: the network is batch-independent, the TTA reduce and the voting run per stream."""
 
-    def __init__(self, model, device="cuda:0", n_streams=8, vote=True, pipeline=False):
+    def __init__(self, model, device="cuda:0", n_streams=8, vote=True, pipeline=False, conv_precision=None):
         """pipeline=True: as StreamRunner(pipeline=True) -- step(batched, poses, next_batched=...) runs the encoder of the NEXT batch
         on a second HIP stream beside the decoder of the current one, and the three aux heads nobody reads are not computed.
-        Same kernels, same results as pipeline=False."""
+        Same kernels, same results as pipeline=False.  conv_precision: as StreamRunner."""
         self.device = torch.device(device)
         self.model = model.to(self.device).eval()
+        set_conv_precision(self.model, conv_precision)
         self.n = n_streams
         self.voters = [VoxelVoter(self.device) for _ in range(n_streams)] if vote else None
         self.memory = None

@@ -5,12 +5,20 @@ frame_point_num 160000), stage-2 model + instance voting; prints the IoU report 
     python tools/e2e_sequence.py --steady N   # stage 1 + voxel voting + --device-preprocess on N >= 200 scans: a warm-up
                                               # run, then a second run_sequence call on the same model (warm page cache)
                                               # timed on its own: steady-state scans/s of the deployable loop
+    --conv-precision {fp32,bf16}              # the engine's convolution precision (default fp32)
 """
 import os, sys, tempfile, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from streammos_amd import kitti, run_sequence, synth
 steady = "--steady" in sys.argv
+prec = "fp32"
+if "--conv-precision" in sys.argv:
+    i = sys.argv.index("--conv-precision")
+    prec = sys.argv[i + 1]
+    if prec not in ("fp32", "bf16"):
+        sys.exit("--conv-precision: fp32 or bf16")
+    del sys.argv[i:i + 2]
 args = [a for a in sys.argv[1:] if a != "--steady"]
 n = int(args[0]) if args else (200 if steady else 24)
 root = tempfile.mkdtemp(prefix="smos_seq_")
@@ -28,16 +36,18 @@ if steady:
     for rep in ("warm-up", "timed"):
         torch.cuda.synchronize()
         t = time.perf_counter()
-        res = run_sequence.run_sequence(model, seq, os.path.join(root, "out_steady"), "cuda:0", vote=True, device_preprocess=True)
+        res = run_sequence.run_sequence(model, seq, os.path.join(root, "out_steady"), "cuda:0", vote=True, device_preprocess=True,
+                                        conv_precision=prec)
         torch.cuda.synchronize()          # run_sequence returns after its last file is written; nothing is left queued
         dt = time.perf_counter() - t
-        print("steady %s: stage 1 + voxel voting + device preprocessing, %d scans: %.1f scans/s (%.2f ms/scan, disk IO "
-              "and runner set-up included)" % (rep, n, n / dt, 1e3 * dt / n), res, flush=True)
+        print("steady %s (conv %s): stage 1 + voxel voting + device preprocessing, %d scans: %.1f scans/s (%.2f ms/scan, disk IO "
+              "and runner set-up included)" % (rep, prec, n, n / dt, 1e3 * dt / n), res, flush=True)
     sys.exit(0)
 for seg, vote, devpre in ((False, True, False), (True, "instance", False), (True, "instance", True)):
     model = run_sequence.load_model(None, "cuda:0", seg=seg)
     t = time.time()
-    res = run_sequence.run_sequence(model, seq, os.path.join(root, "out_%d%d" % (seg, devpre)), "cuda:0", vote=vote, device_preprocess=devpre)
+    res = run_sequence.run_sequence(model, seq, os.path.join(root, "out_%d%d" % (seg, devpre)), "cuda:0", vote=vote, device_preprocess=devpre,
+                                    conv_precision=prec)
     dt = time.time() - t
     print("seg=%s vote=%s device_preprocess=%s  %.1f ms/scan (disk IO included)" % (seg, vote, devpre, 1e3 * dt / n), res, flush=True)
 import numpy as np
