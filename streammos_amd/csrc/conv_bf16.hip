@@ -428,21 +428,16 @@ extern "C" int smos_conv_bf16_cl(const float* x, int64_t x_pitch, const uint16_t
                                  int64_t res_pitch, float* out, int64_t out_pitch, int64_t B, int64_t H, int64_t W, int64_t Cin,
                                  int64_t Cout, int32_t KH, int32_t KW, int32_t stride, int32_t pad_h, int32_t pad_w, int32_t act,
                                  float* chan_sums, smos_stream_t stream) {
-  SMOS_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0 && Cout <= 2048,
-               "conv_bf16_cl: Cin and Cout must be multiples of 32, Cout <= 2048");
+  SMOS_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0,
+               "conv_bf16_cl: Cin and Cout must be multiples of 32");
   SMOS_REQUIRE(KH >= 1 && KW >= 1 && KH <= 7 && KW <= 7 && (stride == 1 || stride == 2) && pad_h >= 0 && pad_w >= 0 &&
                    act >= 0 && act <= 2, "conv_bf16_cl: kernel up to 7 x 7, stride 1 or 2");
   const int64_t Ho = (H + 2 * pad_h - KH) / stride + 1, Wo = (W + 2 * pad_w - KW) / stride + 1;
   SMOS_REQUIRE(H + 2 * pad_h >= KH && W + 2 * pad_w >= KW && Ho > 0 && Wo > 0, "conv_bf16_cl: empty output");
-  SMOS_REQUIRE(x && wprep && out && x_pitch >= Cin && out_pitch >= Cout && x_pitch % 4 == 0 && out_pitch % 4 == 0 &&
-                   (!res || (res_pitch >= Cout && res_pitch % 4 == 0)), "conv_bf16_cl: null pointer / bad pitch");
-  SMOS_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(res) |
-                 reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(wprep)) & 15) == 0,
-               "conv_bf16_cl: pointers must be 16-byte aligned");
-  SMOS_REQUIRE(B * H * W * x_pitch * 4 < (1LL << 31) && B * Ho * Wo * out_pitch * 4 < (1LL << 31) &&
-                   (!res || B * Ho * Wo * res_pitch * 4 < (1LL << 31)), "conv_bf16_cl: a tensor larger than 2 GiB (32-bit buffer offsets)");
-  SMOS_REQUIRE(!chan_sums || (!res && (reinterpret_cast<uintptr_t>(chan_sums) & 15) == 0),
-               "conv_bf16_cl: channel sums need res == NULL and 16-byte alignment");
+  ConvBytes nb;
+  if (int rc = conv_check_operands("conv_bf16_cl", x, x_pitch, wprep, bias, res, res_pitch, out, out_pitch, chan_sums, Cin, Cout,
+                                   B * H * W, B * Ho * Wo, &nb))
+    return rc;
   Bf16Cfg c;
   SMOS_REQUIRE(pick_cfg(B, Ho, Wo, Cout, KH, KW, stride, res != nullptr, &c),
                "conv_bf16_cl: no block shape fits this kernel / stride (smos_conv_bf16_cl_supported)");
@@ -462,11 +457,11 @@ extern "C" int smos_conv_bf16_cl(const float* x, int64_t x_pitch, const uint16_t
   a.nct = (int)nct; a.hb = (int)hb; a.xt = (int)xt; a.hq = (int)((Ho + 3) / 4);
   a.n_items = (int)(B * hb * xt * nct);
   a.rr = c.rr; a.cc = c.cc; a.n_units = c.rr * c.cc * 4;
-  a.slope = act == 0 ? 1.0f : act == 1 ? 0.0f : 0.01f;
+  a.slope = act_slope(act);
   SMOS_STAMPS_HOST(a);
-  a.x_bytes = (int)(B * H * W * x_pitch * 4);
-  a.r_bytes = res ? (int)(B * Ho * Wo * res_pitch * 4) : 0;
-  a.o_bytes = (int)(B * Ho * Wo * out_pitch * 4);
+  a.x_bytes = nb.x;
+  a.r_bytes = nb.r;
+  a.o_bytes = nb.o;
   a.w_bytes = (int)(Cout * Cin * KH * KW * 2);
   a.cout = (int)Cout;
   const hipStream_t s = (hipStream_t)stream;

@@ -1,4 +1,5 @@
-// Shared by csrc/conv_igemm.hip and csrc/conv_rows.hip: argument block, ring barrier, scheduling fence, half-wave sum.
+// Shared by the conv kernels: argument block, ring barrier, scheduling fence, half-wave sum (csrc/conv_igemm.hip and
+// csrc/conv_rows.hip) and the host-side operand checks of every conv entry point.
 #pragma once
 #include "smos_common.h"
 #include "conv_diag.h"
@@ -65,5 +66,36 @@ struct ConvTile {      // where a wave's 32-pixel row segment lies (everything s
   int b, y, x0, ct;
   bool valid;
 };
+
+// Host side, shared by the extern "C" entry points of the conv kernels (`who`: the entry point's name, the prefix of its
+// error messages).  An entry point keeps its own shape rules and checks them first (the pixel counts here are positive).
+struct ConvBytes {
+  int x, r, o;         // B * H * W * x_pitch * 4, B * Ho * Wo * res_pitch * 4 (0 without a residual), B * Ho * Wo * out_pitch * 4
+};
+
+// The operand rules every conv kernel has: x / wprep / out present, row pitches (floats) that cover the channels and keep
+// rows 16-byte aligned, every pointer 16-byte aligned, every map below 2 GiB (the kernels address through 32-bit buffer
+// offsets; the byte counts come back in *bytes), at most 2048 output channels, channel sums only without a residual.
+// res / chan_sums are null where the kernel takes none.
+inline int conv_check_operands(const char* who, const void* x, int64_t x_pitch, const void* wprep, const void* bias, const void* res,
+                               int64_t res_pitch, const void* out, int64_t out_pitch, const void* chan_sums, int64_t Cin,
+                               int64_t Cout, int64_t in_pixels, int64_t out_pixels, ConvBytes* bytes) {
+  SMOS_REQUIRE(Cout <= 2048, "%s: more than 2048 output channels", who);
+  SMOS_REQUIRE(x && wprep && out && x_pitch >= Cin && out_pitch >= Cout && x_pitch % 4 == 0 && out_pitch % 4 == 0 &&
+                   (!res || (res_pitch >= Cout && res_pitch % 4 == 0)), "%s: null pointer / bad pitch", who);
+  SMOS_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(res) |
+                 reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(wprep) | reinterpret_cast<uintptr_t>(chan_sums)) & 15) == 0,
+               "%s: pointers must be 16-byte aligned", who);
+  SMOS_REQUIRE(in_pixels * x_pitch * 4 < (1LL << 31) && out_pixels * out_pitch * 4 < (1LL << 31) &&
+                   (!res || out_pixels * res_pitch * 4 < (1LL << 31)), "%s: a tensor larger than 2 GiB (32-bit buffer offsets)", who);
+  SMOS_REQUIRE(!(chan_sums && res), "%s: channel sums need res == NULL", who);
+  bytes->x = (int)(in_pixels * x_pitch * 4);
+  bytes->r = res ? (int)(out_pixels * res_pitch * 4) : 0;
+  bytes->o = (int)(out_pixels * out_pitch * 4);
+  return SMOS_OK;
+}
+
+// activation code of the C ABI (0 none, 1 ReLU, 2 LeakyReLU) -> slope of max(v, 0) + slope * min(v, 0)
+inline float act_slope(int act) { return act == 0 ? 1.0f : act == 1 ? 0.0f : 0.01f; }
 
 }  // namespace smos

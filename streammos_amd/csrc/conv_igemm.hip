@@ -415,15 +415,12 @@ extern "C" int smos_conv_cl(const float* x, int64_t x_pitch, const float* wprep,
   SMOS_REQUIRE(KH >= 1 && KW >= 1 && KH <= 7 && KW <= 7 && (stride == 1 || stride == 2) && pad_h >= 0 && pad_w >= 0 &&
                    act >= 0 && act <= 2, "conv_cl: kernel up to 7 x 7, stride 1 or 2");
   const int64_t Ho = (H + 2 * pad_h - KH) / stride + 1, Wo = (W + 2 * pad_w - KW) / stride + 1;
-  SMOS_REQUIRE(Ho > 0 && Wo > 0 && Cout <= 2048, "conv_cl: empty output / more than 2048 output channels");
-  SMOS_REQUIRE(x && wprep && out && x_pitch >= Cin && out_pitch >= Cout && x_pitch % 4 == 0 && out_pitch % 4 == 0 &&
-                   (!res || (res_pitch >= Cout && res_pitch % 4 == 0)), "conv_cl: null pointer / bad pitch");
-  SMOS_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(res) |
-                 reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(wprep)) & 15) == 0,
-               "conv_cl: pointers must be 16-byte aligned");
+  SMOS_REQUIRE(Ho > 0 && Wo > 0, "conv_cl: empty output");
+  ConvBytes nb;
+  if (int rc = conv_check_operands("conv_cl", x, x_pitch, wprep, bias, res, res_pitch, out, out_pitch, chan_sums, Cin, Cout,
+                                   B * H * W, B * Ho * Wo, &nb))
+    return rc;
   const int64_t hq = (Ho + 3) / 4, xt = (Wo + 31) / 32, nct = Cout / (32 * mt);
-  SMOS_REQUIRE(B * H * W * x_pitch * 4 < (1LL << 31) && B * Ho * Wo * out_pitch * 4 < (1LL << 31) &&
-                   (!res || B * Ho * Wo * res_pitch * 4 < (1LL << 31)), "conv_cl: a tensor larger than 2 GiB (32-bit buffer offsets)");
   SMOS_REQUIRE(B * hq * xt * nct < (1LL << 30) && (int64_t)KH * KW * (Cin / 32) * nct < (1LL << 20), "conv_cl: too many tiles");
   ConvArgs a;
   a.x = x; a.w = reinterpret_cast<const float4*>(wprep); a.bias = bias; a.res = res; a.out = out; a.sums = chan_sums;
@@ -432,14 +429,13 @@ extern "C" int smos_conv_cl(const float* x, int64_t x_pitch, const float* wprep,
   a.KH = KH; a.KW = KW; a.S = stride; a.PH = pad_h; a.PW = pad_w;
   a.nch = (int)(Cin / 32); a.nstage = KH * KW * a.nch; a.nct = (int)nct;
   a.hq = (int)hq; a.xt = (int)xt; a.n_items = (int)(B * hq * xt * nct);
-  a.slope = act == 0 ? 1.0f : act == 1 ? 0.0f : 0.01f;
-  a.x_bytes = (int)(B * H * W * x_pitch * 4);
+  a.slope = act_slope(act);
+  a.x_bytes = nb.x;
   SMOS_STAMPS_HOST(a);
-  a.r_bytes = res ? (int)(B * Ho * Wo * res_pitch * 4) : 0;
-  a.o_bytes = (int)(B * Ho * Wo * out_pitch * 4);
+  a.r_bytes = nb.r;
+  a.o_bytes = nb.o;
   a.cout = (int)Cout;
   if (chan_sums) {
-    SMOS_REQUIRE(!res && (reinterpret_cast<uintptr_t>(chan_sums) & 15) == 0, "conv_cl: channel sums need res == NULL and 16-byte alignment");
     if (mt == 1) return launch_conv<1, false, true>(a, (hipStream_t)stream);
     if (mt == 2) return launch_conv<2, false, true>(a, (hipStream_t)stream);
     return launch_conv<4, false, true>(a, (hipStream_t)stream);

@@ -349,18 +349,15 @@ extern "C" int smos_conv_rows_cl(const float* x, int64_t x_pitch, const float* w
                                  int64_t res_pitch, float* out, int64_t out_pitch, int64_t B, int64_t H, int64_t W, int64_t Cin,
                                  int64_t Cout, int32_t KH, int32_t KW, int32_t mt, int32_t act, float* chan_sums,
                                  smos_stream_t stream) {
-  SMOS_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && (mt == 1 || mt == 2) && Cout % (32 * mt) == 0 &&
-                   Cout <= 2048, "conv_rows_cl: Cin a multiple of 32, Cout of 32 * mt (mt in {1, 2}; Cout <= 2048)");
+  SMOS_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 32 == 0 && (mt == 1 || mt == 2) && Cout % (32 * mt) == 0,
+               "conv_rows_cl: Cin a multiple of 32, Cout of 32 * mt (mt in {1, 2})");
   SMOS_REQUIRE(KH >= 1 && KH <= 7 && (KH & 1) && (KW == 3 || KW == 5 || KW == 7) && act >= 0 && act <= 2,
                "conv_rows_cl: odd KH <= 7, KW in {3, 5, 7}");
-  SMOS_REQUIRE(x && wprep && out && x_pitch >= Cin && out_pitch >= Cout && x_pitch % 4 == 0 && out_pitch % 4 == 0 &&
-                   (!res || (res_pitch >= Cout && res_pitch % 4 == 0)) && !(res && chan_sums), "conv_rows_cl: null pointer / bad pitch");
-  SMOS_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(res) |
-                 reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(wprep) | reinterpret_cast<uintptr_t>(chan_sums)) & 15) == 0,
-               "conv_rows_cl: pointers must be 16-byte aligned");
+  ConvBytes nb;
+  if (int rc = conv_check_operands("conv_rows_cl", x, x_pitch, wprep, bias, res, res_pitch, out, out_pitch, chan_sums, Cin, Cout,
+                                   B * H * W, B * H * W, &nb))
+    return rc;
   const int64_t hq = (H + 3) / 4, xt = (W + 31) / 32, nct = Cout / (32 * mt);
-  SMOS_REQUIRE(B * H * W * x_pitch * 4 < (1LL << 31) && B * H * W * out_pitch * 4 < (1LL << 31) &&
-                   (!res || B * H * W * res_pitch * 4 < (1LL << 31)), "conv_rows_cl: a tensor larger than 2 GiB (32-bit buffer offsets)");
   SMOS_REQUIRE(B * hq * xt * nct < (1LL << 30) && (int64_t)KH * KW * (Cin / 32) * nct < (1LL << 20), "conv_rows_cl: too many tiles");
   ConvArgs a;
   a.x = x; a.w = reinterpret_cast<const float4*>(wprep); a.bias = bias; a.res = res; a.out = out; a.sums = chan_sums;
@@ -369,11 +366,11 @@ extern "C" int smos_conv_rows_cl(const float* x, int64_t x_pitch, const float* w
   a.KH = KH; a.KW = KW; a.S = 1; a.PH = KH / 2; a.PW = KW / 2;
   a.nch = (int)(Cin / 32); a.nstage = KH * KW * a.nch; a.nct = (int)nct;
   a.hq = (int)hq; a.xt = (int)xt; a.n_items = (int)(B * hq * xt * nct);
-  a.slope = act == 0 ? 1.0f : act == 1 ? 0.0f : 0.01f;
-  a.x_bytes = (int)(B * H * W * x_pitch * 4);
+  a.slope = act_slope(act);
+  a.x_bytes = nb.x;
   SMOS_STAMPS_HOST_NONE(a);
-  a.r_bytes = res ? (int)(B * H * W * res_pitch * 4) : 0;
-  a.o_bytes = (int)(B * H * W * out_pitch * 4);
+  a.r_bytes = nb.r;
+  a.o_bytes = nb.o;
   a.cout = (int)Cout;
   hipStream_t s = (hipStream_t)stream;
 #define SMOS_ROWS_DISPATCH(KW_)                                                                  \

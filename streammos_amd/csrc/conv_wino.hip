@@ -88,26 +88,21 @@ extern "C" int smos_conv_wino_cl(const float* x, int64_t x_pitch, const float* w
                                  int64_t Cout, int32_t mb, int32_t act, float* chan_sums, smos_stream_t stream) {
   SMOS_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 16 == 0 && (mb == 1 || mb == 2) && Cout % (16 * mb) == 0 &&
                    act >= 0 && act <= 2, "conv_wino_cl: Cin must be a multiple of 16 and Cout of 16 * mb (mb in {1, 2})");
-  SMOS_REQUIRE(Cout <= 2048, "conv_wino_cl: more than 2048 output channels");
-  SMOS_REQUIRE(x && wprep && out && x_pitch >= Cin && out_pitch >= Cout && x_pitch % 4 == 0 && out_pitch % 4 == 0 &&
-                   (!res || (res_pitch >= Cout && res_pitch % 4 == 0)), "conv_wino_cl: null pointer / bad pitch");
-  SMOS_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(res) |
-                 reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(wprep) | reinterpret_cast<uintptr_t>(chan_sums)) & 15) == 0,
-               "conv_wino_cl: pointers must be 16-byte aligned");
-  SMOS_REQUIRE(B * H * W * x_pitch * 4 < (1LL << 31) && B * H * W * out_pitch * 4 < (1LL << 31) &&
-                   (!res || B * H * W * res_pitch * 4 < (1LL << 31)), "conv_wino_cl: a tensor larger than 2 GiB (32-bit buffer offsets)");
+  ConvBytes nb;
+  if (int rc = conv_check_operands("conv_wino_cl", x, x_pitch, wprep, bias, res, res_pitch, out, out_pitch, chan_sums, Cin, Cout,
+                                   B * H * W, B * H * W, &nb))
+    return rc;
   const int64_t yb = (H + 7) / 8, xb = (W + 31) / 32, nct = Cout / (16 * mb);
   SMOS_REQUIRE(B * yb * xb * nct < (1LL << 30) && nct * (Cin / 16) < (1LL << 24), "conv_wino_cl: too many tiles");
-  SMOS_REQUIRE(!(chan_sums && res), "conv_wino_cl: channel sums need res == NULL");
   WinoArgs a;
   a.x = x; a.w = reinterpret_cast<const float4*>(wprep); a.bias = bias; a.res = res; a.out = out; a.sums = chan_sums;
   a.xp = x_pitch; a.rp = res_pitch; a.op = out_pitch;
   a.B = (int)B; a.H = (int)H; a.W = (int)W;
   a.nchunk = (int)(Cin / 16); a.nct = (int)nct; a.yb = (int)yb; a.xb = (int)xb; a.n_items = (int)(B * yb * xb * nct);
-  a.slope = act == 0 ? 1.0f : act == 1 ? 0.0f : 0.01f;
-  a.x_bytes = (int)(B * H * W * x_pitch * 4);
-  a.r_bytes = res ? (int)(B * H * W * res_pitch * 4) : 0;
-  a.o_bytes = (int)(B * H * W * out_pitch * 4);
+  a.slope = act_slope(act);
+  a.x_bytes = nb.x;
+  a.r_bytes = nb.r;
+  a.o_bytes = nb.o;
   a.cout = (int)Cout;
   hipStream_t s = (hipStream_t)stream;
   if (chan_sums) return mb == 1 ? launch_wino<1, false, true>(a, s) : launch_wino<2, false, true>(a, s);

@@ -333,13 +333,10 @@ extern "C" int smos_conv_wino1d_cl(const float* x, int64_t x_pitch, const float*
   SMOS_REQUIRE(l_is_y || l_is_x, "conv_wino1d_cl: kernel must be 5x3, 7x3, 3x5 or 3x7");
   SMOS_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && Cin % 16 == 0 && (mb == 1 || mb == 2) && Cout % (16 * mb) == 0 &&
                    act >= 0 && act <= 2, "conv_wino1d_cl: Cin must be a multiple of 16 and Cout of 16 * mb (mb in {1, 2})");
-  SMOS_REQUIRE(Cout <= 2048, "conv_wino1d_cl: more than 2048 output channels");
-  SMOS_REQUIRE(x && wprep && out && x_pitch >= Cin && out_pitch >= Cout && x_pitch % 4 == 0 && out_pitch % 4 == 0,
-               "conv_wino1d_cl: null pointer / bad pitch");
-  SMOS_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(bias) |
-                 reinterpret_cast<uintptr_t>(wprep)) & 15) == 0, "conv_wino1d_cl: pointers must be 16-byte aligned");
-  SMOS_REQUIRE(B * H * W * x_pitch * 4 < (1LL << 31) && B * H * W * out_pitch * 4 < (1LL << 31),
-               "conv_wino1d_cl: a tensor larger than 2 GiB (32-bit buffer offsets)");
+  ConvBytes nb;      // no residual, no channel sums
+  if (int rc = conv_check_operands("conv_wino1d_cl", x, x_pitch, wprep, bias, nullptr, 0, out, out_pitch, nullptr, Cin, Cout,
+                                   B * H * W, B * H * W, &nb))
+    return rc;
   const int64_t nL = l_is_y ? H : W, nS = l_is_y ? W : H, KL = l_is_y ? KH : KW;
   const int64_t lb = (nL + 15) / 16, sb = (nS + 31) / 32, nct = Cout / (16 * mb);
   SMOS_REQUIRE(B * lb * sb * nct < (1LL << 30) && nct * (Cin / 16) < (1LL << 24), "conv_wino1d_cl: too many tiles");
@@ -349,9 +346,9 @@ extern "C" int smos_conv_wino1d_cl(const float* x, int64_t x_pitch, const float*
   a.B = (int)B; a.nL = (int)nL; a.nS = (int)nS;
   a.sL = l_is_y ? (int)W : 1; a.sS = l_is_y ? 1 : (int)W;
   a.nchunk = (int)(Cin / 16); a.nct = (int)nct; a.lb = (int)lb; a.sb = (int)sb; a.n_items = (int)(B * lb * sb * nct);
-  a.slope = act == 0 ? 1.0f : act == 1 ? 0.0f : 0.01f;
-  a.x_bytes = (int)(B * H * W * x_pitch * 4);
-  a.o_bytes = (int)(B * H * W * out_pitch * 4);
+  a.slope = act_slope(act);
+  a.x_bytes = nb.x;
+  a.o_bytes = nb.o;
   a.cout = (int)Cout;
   hipStream_t s = (hipStream_t)stream;
   if (KL == 7) return mb == 1 ? launch_wino1d<7, 1>(a, s) : launch_wino1d<7, 2>(a, s);

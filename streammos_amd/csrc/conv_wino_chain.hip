@@ -139,7 +139,7 @@ extern "C" int smos_conv_wino_chain_cl(int32_t n_layers, const float* x0, int64_
                  "conv_wino_chain_cl: pointers must be 16-byte aligned");
     c.x[L] = xin; c.w[L] = reinterpret_cast<const float4*>(wprep[L]); c.bias[L] = bias[L]; c.res[L] = r; c.out[L] = outs[L];
     c.xp[L] = xpitch; c.rp[L] = rp; c.op[L] = out_pitches[L];
-    c.slope[L] = acts[L] == 0 ? 1.0f : acts[L] == 1 ? 0.0f : 0.01f;
+    c.slope[L] = act_slope(acts[L]);
     c.x_bytes[L] = (int)(B * H * W * xpitch * 4);
     c.r_bytes[L] = r ? (int)(B * H * W * rp * 4) : 0;
     c.o_bytes[L] = (int)(B * H * W * out_pitches[L] * 4);

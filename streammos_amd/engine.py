@@ -70,7 +70,7 @@ class InferenceEngine:
         self.layout = layout
         self.conv_precision = conv_precision
         self._bf16 = conv_precision == "bf16"
-        self._conv_route = {}           # bf16 mode: weight -> whether its last launch ran in bf16 (False: fp32 fallback)
+        self._conv_layers = {}          # id(folded weight) -> ops.ConvLayer (which holds the weight): see _conv
         self.device = next(net.parameters()).device
         self.bev_hw = tuple(net.bev_wl_shape)
         enc = net.bev_net
@@ -188,8 +188,6 @@ class InferenceEngine:
         self.pool_fused = os.environ.get("SMOS_POOL_FUSED", "1") != "0"   # DownSample2D pool branch + tail in one launch (A/B switch)
         self.block_call = os.environ.get("SMOS_BLOCK_CALL", "1") != "0"   # BasicBlock = one foreign call (A/B switch; same launches)
         self.wino_chain = os.environ.get("SMOS_WINO_CHAIN", "0") == "1"   # EXPERIMENTAL: runs of BasicBlocks as one dataflow launch
-        self._wprep = {}
-        self._wino_plan = {}
         if self._bf16:
             # the block calls and the wino chain launch fp32 kernels: bf16 mode takes the launch-by-launch path
             self.block_call = False
@@ -427,25 +425,29 @@ class InferenceEngine:
         """bf16 mode: {"bf16": layers whose last launch ran on the bf16 kernel, "fallback": layers that stayed on the fp32
         path (shapes the bf16 kernel does not cover)}; one entry per layer, so after a step these are that step's counts.
         fp32 mode: both 0."""
-        n16 = sum(1 for v in self._conv_route.values() if v)
-        return {"bf16": n16, "fallback": len(self._conv_route) - n16}
+        ran = [layer.ran_bf16 for layer in self._conv_layers.values() if layer.ran_bf16 is not None]
+        return {"bf16": sum(ran), "fallback": len(ran) - sum(ran)}
+
+    def _conv_layer(self, w):
+        """The ops.ConvLayer of a folded weight, made on first use.  Keyed by id(w): the layer holds w, so the id stays w's."""
+        layer = self._conv_layers.get(id(w))
+        if layer is None:
+            layer = self._conv_layers[id(w)] = ops.ConvLayer(w)
+        return layer
 
     def _conv(self, x, w, bias, act, stride=1, residual=None, out=None, chan_sums=None):
         """act(conv(x, w) + bias [+ residual]) for a folded weight w [Cout, Cin, KH, KW] ("same" padding for odd kernels)
-        on channels-last maps: one launch of csrc/conv_igemm.hip; the operand-ordered copy of w is made once per (weight,
-        mt).  With SMOS_OWN_CONV=0: MIOpen conv + the separate bias / activation / residual pass.  conv_precision "bf16":
-        csrc/conv_bf16.hip where it covers the shape, else the fp32 path below (counted in conv_precision_stats)."""
+        on channels-last maps: one launch of the kernel ops.conv_route names; the operand-ordered copies of w are made once,
+        in the weight's ops.ConvLayer.  With SMOS_OWN_CONV=0: MIOpen conv + the separate bias / activation / residual pass.
+        conv_precision "bf16": csrc/conv_bf16.hip where it covers the shape, else the fp32 path below (counted in
+        conv_precision_stats)."""
         cout, cin, kh, kw = w.shape
+        layer = self._conv_layer(w)
         if self._bf16:
-            ok = self.own_conv and ops.conv_bf16_ok(x, cout, (kh, kw), stride, residual, out, chan_sums)
-            self._conv_route[w.data_ptr()] = ok
-            if ok:
-                key = (w.data_ptr(), "bf16")          # never collides with the fp32 packings' keys
-                wp = self._wprep.get(key)
-                if wp is None:
-                    wp = self._wprep[key] = ops.conv_bf16_prepare(w)
-                return ops.conv_bf16_cl(x, wp, bias, act, cout, (kh, kw), stride=stride, residual=residual, out=out,
-                                        chan_sums=chan_sums)
+            layer.ran_bf16 = self.own_conv and ops.conv_bf16_ok(x, cout, (kh, kw), stride, residual, out, chan_sums)
+            if layer.ran_bf16:
+                return ops.conv_bf16_cl(x, layer.operand("bf16"), bias, act, cout, (kh, kw), stride=stride, residual=residual,
+                                        out=out, chan_sums=chan_sums)
         # fast accept (no per-launch predicate walk): channel counts the MFMA tiling covers and operands far below the 2 GiB of the
         # 32-bit buffer offsets (<= 2^26 input floats; a slice's pitch is at most twice its channels, Cout at most four times Cin)
         easy = (cin % 32 == 0 and cout % 32 == 0 and cout <= 4 * cin and kh <= 7 and kw <= 7 and (stride == 1 or stride == 2) and
@@ -460,37 +462,22 @@ class InferenceEngine:
             return ops.bias_act_cl(y, bias, act, out=out if out is not None else y, residual=residual)
         b, _, h, wd = x.shape
         ho, wo = (h + 2 * (kh // 2) - kh) // stride + 1, (wd + 2 * (kw // 2) - kw) // stride + 1
-        if self.wino and kh == 3 and kw == 3 and stride == 1 and cin % 16 == 0 and cout % 16 == 0:      # = ops.conv_wino_ok
+        route = ops.conv_route(cin, cout, (kh, kw), stride, b * ho * wo, residual is not None, chan_sums is not None, self)
+        family, tile = route
+        wp = layer.operand(route)
+        if family == "wino":
             # stride-1 3x3: Winograd F(2x2, 3x3) on the matrix cores (csrc/conv_wino.hip): 4 instead of 9 multiply-adds per
             # output and channel pair, fp32 throughout (weights transformed in float64 on the host); 1.35-1.7x the direct
             # kernels per layer (tools/ubench_wino.py), logits within 2e-6 of the reference's (tests/test_gpu_e2e.py)
-            plan = self._wino_plan.get(id(w))          # the folded weight tensors live as long as the engine: id() is stable
-            if plan is None:
-                mb = ops.conv_wino_mb(cout)
-                plan = self._wino_plan[id(w)] = (ops.conv_wino_prepare(w, mb), mb, w)
-            return ops.conv_wino_cl(x, plan[0], bias, act, cout, mb=plan[1], residual=residual, out=out, chan_sums=chan_sums)
-        if self.wino1d and ops.conv_wino1d_ok((kh, kw), stride, cin, cout, residual, chan_sums):
+            return ops.conv_wino_cl(x, wp, bias, act, cout, mb=tile, residual=residual, out=out, chan_sums=chan_sums)
+        if family == "wino1d":
             # the k x 3 / 3 x k branches of the Unbalance blocks: 1-D Winograd F(2, 3) along the 3-tap axis (csrc/conv_wino1d.hip)
-            mb = ops.conv_wino_mb(cout)
-            key = (w.data_ptr(), "wino1d", mb)
-            wp = self._wprep.get(key)
-            if wp is None:
-                wp = self._wprep[key] = ops.conv_wino1d_prepare(w, mb)
-            return ops.conv_wino1d_cl(x, wp, bias, act, cout, (kh, kw), mb=mb, out=out)
-        mt = ops.conv_mt(cout, b * ho * wo, residual is not None)
-        if self.conv_rows and mt <= self.conv_rows_mt and ops.conv_rows_ok((kh, kw), stride, cin, cout) and kw >= self.conv_rows:
+            return ops.conv_wino1d_cl(x, wp, bias, act, cout, (kh, kw), mb=tile, out=out)
+        if family == "rows":
             # the row-staging variant (csrc/conv_rows.hip): per layer within 0 .. -5 % of conv_igemm alone on the GPU, +1 % in the
             # two-stream step (241.9 vs 239.1 scans/s: a fifth of the L1 requests leaves more of the memory path to the other stream)
-            key = (w.data_ptr(), "rows", mt)
-            wp = self._wprep.get(key)
-            if wp is None:
-                wp = self._wprep[key] = ops.conv_prepare(w, mt, order="rows")
-            return ops.conv_rows_cl(x, wp, bias, act, cout, (kh, kw), mt=mt, residual=residual, out=out, chan_sums=chan_sums)
-        key = (w.data_ptr(), mt)
-        wp = self._wprep.get(key)
-        if wp is None:
-            wp = self._wprep[key] = ops.conv_prepare(w, mt)
-        return ops.conv_cl(x, wp, bias, act, cout, (kh, kw), stride=stride, mt=mt, residual=residual, out=out, chan_sums=chan_sums)
+            return ops.conv_rows_cl(x, wp, bias, act, cout, (kh, kw), mt=tile, residual=residual, out=out, chan_sums=chan_sums)
+        return ops.conv_cl(x, wp, bias, act, cout, (kh, kw), stride=stride, mt=tile, residual=residual, out=out, chan_sums=chan_sums)
 
     def _block_cl(self, x, p, out=None):
         if p.kind == "down":
@@ -548,8 +535,9 @@ class InferenceEngine:
                 (not self._bf16 or ops.conv_bf16_ok(y, c, tuple(p.w2.shape[2:]), chan_sums=True))):
             # the conv's epilogue leaves the per-row-segment channel sums behind: no pass over y2 for the average pool
             # (bf16 mode: the bf16 kernel writes them, in the table layout of conv_cl)
-            wino = not self._bf16 and self.wino and ops.conv_wino_ok(tuple(p.w2.shape[2:]), 1, c, c)
-            chunks = ops.conv_wino_sum_chunks(h, w) if wino else ops.conv_sum_chunks(h, w)
+            # the table's layout is the kernel's, so the function that picks the kernel in _conv picks it here
+            family = "bf16" if self._bf16 else ops.conv_route(c, c, tuple(p.w2.shape[2:]), 1, bsz * h * w, False, True, self)[0]
+            chunks = ops.conv_wino_sum_chunks(h, w) if family == "wino" else ops.conv_sum_chunks(h, w)
             ws = self._block_ws(p, bsz * c * (chunks + 1))
             sums = ws[:bsz * chunks * c].view(bsz, chunks, c)
             y2 = self._conv(y, p.w2, None, NONE, chan_sums=sums)

@@ -3,6 +3,7 @@
 torch is used for device memory and streams only: every function launches on
 ``torch.cuda.current_stream`` of the tensors' device and returns without synchronising.
 """
+import collections
 import ctypes
 import os
 
@@ -579,7 +580,7 @@ def conv_prepare(w, mt, order="taps"):
 
 
 def conv_cl_supported(x, cout, kernel, stride=1, residual=None, out=None):
-    """The hard limits of smos_conv_cl / smos_conv_rows_cl (the SMOS_REQUIREs of csrc/conv_igemm.hip:486-500), as a
+    """The hard limits of smos_conv_cl / smos_conv_rows_cl (the SMOS_REQUIREs of smos_conv_cl and of conv_check_operands, csrc/conv_common.h), as a
     predicate the engine asks BEFORE it routes a layer to the own kernels: Cin / Cout multiples of 32, Cout <= 2048,
     kernel <= 7x7, stride 1 or 2, and every operand below 2 GiB (the kernels address through 32-bit buffer offsets; a
     16-stream batch of 128-channel 256x256 maps is 2.1 GB).  Shapes only: works on meta tensors."""
@@ -607,40 +608,68 @@ def conv_rows_ok(kernel, stride, cin, cout):
     return stride == 1 and kw in (3, 5, 7) and kh in (1, 3, 5, 7) and cin % 32 == 0 and cout % 32 == 0
 
 
+def _conv_operands(name, x, wprep, bias, cout, ho, wo, residual=None, out=None, chan_sums=None, sum_chunks=None):
+    """What the conv wrappers share: the operands live in GPU memory, `out` is allocated (or has the output's shape), `residual`
+    has it too, `chan_sums` is the contiguous float32 [B, sum_chunks(Ho, Wo), Cout] table of the kernel family and comes without
+    a residual.  Returns (out, head): the arguments every conv entry point starts with -- x, x pitch, wprep, bias, res,
+    res pitch, out, out pitch."""
+    _require_cuda(name, x, wprep, bias, residual, out, chan_sums)
+    b = x.shape[0]
+    if out is None:
+        out = empty_cl(b, cout, ho, wo, x.device)
+    elif tuple(out.shape) != (b, cout, ho, wo):
+        raise RuntimeError("%s: out has shape %s, expected %s" % (name, tuple(out.shape), (b, cout, ho, wo)))
+    if residual is not None and tuple(residual.shape) != (b, cout, ho, wo):
+        raise RuntimeError("%s: residual has shape %s" % (name, tuple(residual.shape)))
+    if chan_sums is not None and (residual is not None or not chan_sums.is_contiguous() or chan_sums.dtype != torch.float32 or
+                                  tuple(chan_sums.shape) != (b, sum_chunks(ho, wo), cout)):
+        raise RuntimeError("%s: chan_sums must be contiguous float32 [B, %s(Ho, Wo), Cout], without a residual"
+                           % (name, sum_chunks.__name__))
+    return out, (x.data_ptr(), _cl(name, x), wprep.data_ptr(), bias.data_ptr() if bias is not None else None,
+                 residual.data_ptr() if residual is not None else None, _cl(name, residual) if residual is not None else 0,
+                 out.data_ptr(), _cl(name, out))
+
+
+def _conv_label(name, x, cout, ho, wo, kernel, residual=None):
+    return "%s[%dx%dx%dx%d->%dx%dx%dk%dx%d%s]" % ((name,) + tuple(x.shape) + (cout, ho, wo) + tuple(kernel) +
+                                                ("+res" if residual is not None else "",))
+
+
+def _conv_launch(fn_name, family, args, keep, x, label_fn):
+    """One conv launch of the C function `fn_name` on x's device and torch's current stream.  While nothing is profiled that is
+    all (no label, no span: a label is a string format of ~10 numbers); otherwise the launch carries label_fn() under the
+    kernel family, and a requested replay gets a closure over args (`keep`: the operand tensors, alive as long as it is)."""
+    fn = getattr(_lib.load(), fn_name)
+    dev = x.device
+    if not profiling.enabled():
+        with _on(dev):
+            rc = fn(*args, _raw_stream(_dev_index(dev)))
+        if rc:
+            _lib.check(rc, fn_name)
+        return
+    label = label_fn()
+    with _on(dev), profiling.span(label, family):
+        rc = fn(*args, _stream(x))
+    _lib.check(rc, fn_name)
+    if profiling._replay_label == label:
+        def again(keep=keep):
+            with _on(keep[0].device), profiling.span(label, family):
+                _lib.check(fn(*args, _stream(keep[0])), fn_name)
+        profiling.offer_replay(label, again)
+
+
 def conv_rows_cl(x, wprep, bias, act, cout, kernel, mt=1, residual=None, out=None, chan_sums=None):
     """conv_cl for stride 1 / "same" padding / KW in {3, 5, 7} at 32 * mt (mt in {1, 2}) output channels per block, with the
     input rows staged through LDS once per kernel row instead of one global request per tap (csrc/conv_rows.hip).
     wprep = conv_prepare(w, mt, order="rows")."""
-    _require_cuda("conv_rows_cl", x, wprep, bias, residual, out, chan_sums)
     b, cin, h, w = x.shape
     kh, kw = kernel
     if not conv_rows_ok(kernel, 1, cin, cout) or wprep.numel() != cout * cin * kh * kw or mt not in (1, 2) or cout % (32 * mt):
         raise RuntimeError("conv_rows_cl: unsupported shape %s k%dx%d -> %d" % (tuple(x.shape), kh, kw, cout))
-    if out is None:
-        out = empty_cl(b, cout, h, w, x.device)
-    elif tuple(out.shape) != (b, cout, h, w):
-        raise RuntimeError("conv_rows_cl: out has shape %s" % (tuple(out.shape),))
-    if residual is not None and tuple(residual.shape) != (b, cout, h, w):
-        raise RuntimeError("conv_rows_cl: residual has shape %s" % (tuple(residual.shape),))
-    if chan_sums is not None and (residual is not None or not chan_sums.is_contiguous() or
-                                  tuple(chan_sums.shape) != (b, conv_sum_chunks(h, w), cout)):
-        raise RuntimeError("conv_rows_cl: chan_sums must be contiguous [B, conv_sum_chunks(H, W), Cout], without a residual")
-    lib = _lib.load()
-    label = "conv_cl[%dx%dx%dx%d->%dx%dx%dk%dx%d%s]" % (b, cin, h, w, cout, h, w, kh, kw, "+res" if residual is not None else "")
-    args = (x.data_ptr(), _cl("conv_rows_cl", x), wprep.data_ptr(), bias.data_ptr() if bias is not None else None,
-            residual.data_ptr() if residual is not None else None, _cl("conv_rows_cl", residual) if residual is not None else 0,
-            out.data_ptr(), _cl("conv_rows_cl", out), b, h, w, cin, cout, kh, kw, int(mt), int(act),
-            chan_sums.data_ptr() if chan_sums is not None else None)
-    with _on(x.device), profiling.span(label, "conv_rows"):
-        rc = lib.smos_conv_rows_cl(*args, _stream(x))
-    _lib.check(rc, "smos_conv_rows_cl")
-    if profiling._replay_label == label:
-        keep = (x, wprep, bias, residual, out, chan_sums)
-
-        def again(keep=keep):
-            with _on(keep[0].device), profiling.span(label, "conv_rows"):
-                _lib.check(lib.smos_conv_rows_cl(*args, _stream(keep[0])), "smos_conv_rows_cl")
-        profiling.offer_replay(label, again)
+    out, head = _conv_operands("conv_rows_cl", x, wprep, bias, cout, h, w, residual, out, chan_sums, conv_sum_chunks)
+    args = head + (b, h, w, cin, cout, kh, kw, int(mt), int(act), chan_sums.data_ptr() if chan_sums is not None else None)
+    _conv_launch("smos_conv_rows_cl", "conv_rows", args, (x, wprep, bias, residual, out, chan_sums), x,
+                 lambda: _conv_label("conv_cl", x, cout, h, w, kernel, residual))
     return out
 
 
@@ -668,39 +697,17 @@ def conv_cl(x, wprep, bias, act, cout, kernel, stride=1, padding=None, mt=1, res
     wprep = conv_prepare(w, mt); kernel = (KH, KW); padding defaults to "same" for odd kernels.
     chan_sums: optional float32 [B, conv_sum_chunks(Ho, Wo), Cout] that receives the per-row-segment channel sums of the
     output (the average-pool input of a ChannelAtt block); not together with a residual."""
-    _require_cuda("conv_cl", x, wprep, bias, residual, out, chan_sums)
     b, cin, h, w = x.shape
     kh, kw = kernel
     ph, pw = padding if padding is not None else (kh // 2, kw // 2)
     ho, wo = (h + 2 * ph - kh) // stride + 1, (w + 2 * pw - kw) // stride + 1
     if wprep.numel() != cout * cin * kh * kw:
         raise RuntimeError("conv_cl: weight block has %d floats, expected %d" % (wprep.numel(), cout * cin * kh * kw))
-    if out is None:
-        out = empty_cl(b, cout, ho, wo, x.device)
-    elif tuple(out.shape) != (b, cout, ho, wo):
-        raise RuntimeError("conv_cl: out has shape %s, expected %s" % (tuple(out.shape), (b, cout, ho, wo)))
-    if residual is not None and tuple(residual.shape) != (b, cout, ho, wo):
-        raise RuntimeError("conv_cl: residual has shape %s" % (tuple(residual.shape),))
-    if chan_sums is not None and (residual is not None or not chan_sums.is_contiguous() or chan_sums.dtype != torch.float32 or
-                                  tuple(chan_sums.shape) != (b, conv_sum_chunks(ho, wo), cout)):
-        raise RuntimeError("conv_cl: chan_sums must be contiguous float32 [B, conv_sum_chunks(Ho, Wo), Cout], without a residual")
-    lib = _lib.load()
-    label = ("conv_cl[%dx%dx%dx%d->%dx%dx%dk%dx%d%s]" % (b, cin, h, w, cout, ho, wo, kh, kw, "+res" if residual is not None else "")
-             if profiling.enabled() else None)
-    args = (x.data_ptr(), _cl("conv_cl", x), wprep.data_ptr(), bias.data_ptr() if bias is not None else None,
-            residual.data_ptr() if residual is not None else None, _cl("conv_cl", residual) if residual is not None else 0,
-            out.data_ptr(), _cl("conv_cl", out), b, h, w, cin, cout, kh, kw, stride, ph, pw, mt, int(act),
-            chan_sums.data_ptr() if chan_sums is not None else None)
-    with _on(x.device), profiling.span(label, "conv_igemm"):
-        rc = lib.smos_conv_cl(*args, _stream(x))
-    _lib.check(rc, "smos_conv_cl")
-    if label is not None and profiling._replay_label == label:
-        keep = (x, wprep, bias, residual, out, chan_sums)          # the closure keeps the operands alive
-
-        def again(keep=keep):
-            with _on(keep[0].device), profiling.span(label, "conv_igemm"):
-                _lib.check(lib.smos_conv_cl(*args, _stream(keep[0])), "smos_conv_cl")
-        profiling.offer_replay(label, again)
+    out, head = _conv_operands("conv_cl", x, wprep, bias, cout, ho, wo, residual, out, chan_sums, conv_sum_chunks)
+    args = head + (b, h, w, cin, cout, kh, kw, stride, ph, pw, mt, int(act),
+                   chan_sums.data_ptr() if chan_sums is not None else None)
+    _conv_launch("smos_conv_cl", "conv_igemm", args, (x, wprep, bias, residual, out, chan_sums), x,
+                 lambda: _conv_label("conv_cl", x, cout, ho, wo, kernel, residual))
     return out
 
 
@@ -742,7 +749,6 @@ def conv_bf16_cl(x, wprep, bias, act, cout, kernel, stride=1, padding=None, resi
     with fp32 sums, bias, residual, activation and output.  wprep = conv_bf16_prepare(w); kernel = (KH, KW); padding defaults
     to "same" for odd kernels; chan_sums: float32 [B, conv_sum_chunks(Ho, Wo), Cout] (the layout of conv_cl), not together
     with a residual."""
-    _require_cuda("conv_bf16_cl", x, wprep, bias, residual, out, chan_sums)
     b, cin, h, w = x.shape
     kh, kw = kernel
     ph, pw = padding if padding is not None else (kh // 2, kw // 2)
@@ -752,32 +758,12 @@ def conv_bf16_cl(x, wprep, bias, act, cout, kernel, stride=1, padding=None, resi
                            (cout * cin * kh * kw, wprep.numel(), wprep.dtype))
     if x.dtype != torch.float32 or (bias is not None and (bias.dtype != torch.float32 or bias.numel() != cout)):
         raise RuntimeError("conv_bf16_cl: x and bias must be float32 (bias of Cout entries)")
-    if out is None:
-        out = empty_cl(b, cout, ho, wo, x.device)
-    elif tuple(out.shape) != (b, cout, ho, wo) or out.dtype != torch.float32:
-        raise RuntimeError("conv_bf16_cl: out has shape %s, expected %s" % (tuple(out.shape), (b, cout, ho, wo)))
-    if residual is not None and (tuple(residual.shape) != (b, cout, ho, wo) or residual.dtype != torch.float32):
-        raise RuntimeError("conv_bf16_cl: residual has shape %s" % (tuple(residual.shape),))
-    if chan_sums is not None and (residual is not None or not chan_sums.is_contiguous() or chan_sums.dtype != torch.float32 or
-                                  tuple(chan_sums.shape) != (b, conv_sum_chunks(ho, wo), cout)):
-        raise RuntimeError("conv_bf16_cl: chan_sums must be contiguous float32 [B, conv_sum_chunks(Ho, Wo), Cout], without a residual")
-    lib = _lib.load()
-    label = ("conv_bf16[%dx%dx%dx%d->%dx%dx%dk%dx%d%s]" % (b, cin, h, w, cout, ho, wo, kh, kw, "+res" if residual is not None else "")
-             if profiling.enabled() else None)
-    args = (x.data_ptr(), _cl("conv_bf16_cl", x), wprep.data_ptr(), bias.data_ptr() if bias is not None else None,
-            residual.data_ptr() if residual is not None else None, _cl("conv_bf16_cl", residual) if residual is not None else 0,
-            out.data_ptr(), _cl("conv_bf16_cl", out), b, h, w, cin, cout, kh, kw, stride, ph, pw, int(act),
-            chan_sums.data_ptr() if chan_sums is not None else None)
-    with _on(x.device), profiling.span(label, "conv_bf16"):
-        rc = lib.smos_conv_bf16_cl(*args, _stream(x))
-    _lib.check(rc, "smos_conv_bf16_cl")
-    if label is not None and profiling._replay_label == label:
-        keep = (x, wprep, bias, residual, out, chan_sums)          # the closure keeps the operands alive
-
-        def again(keep=keep):
-            with _on(keep[0].device), profiling.span(label, "conv_bf16"):
-                _lib.check(lib.smos_conv_bf16_cl(*args, _stream(keep[0])), "smos_conv_bf16_cl")
-        profiling.offer_replay(label, again)
+    if (out is not None and out.dtype != torch.float32) or (residual is not None and residual.dtype != torch.float32):
+        raise RuntimeError("conv_bf16_cl: out and residual must be float32")
+    out, head = _conv_operands("conv_bf16_cl", x, wprep, bias, cout, ho, wo, residual, out, chan_sums, conv_sum_chunks)
+    args = head + (b, h, w, cin, cout, kh, kw, stride, ph, pw, int(act), chan_sums.data_ptr() if chan_sums is not None else None)
+    _conv_launch("smos_conv_bf16_cl", "conv_bf16", args, (x, wprep, bias, residual, out, chan_sums), x,
+                 lambda: _conv_label("conv_bf16", x, cout, ho, wo, kernel, residual))
     return out
 
 
@@ -820,43 +806,13 @@ def conv_wino_cl(x, wprep, bias, act, cout, mb=2, residual=None, out=None, chan_
     """act(conv3x3(x) + bias [+ residual]) (stride 1, "same" padding) on channels-last [B,C,H,W] views in one launch of the
     Winograd F(2x2, 3x3) kernel (csrc/conv_wino.hip).  wprep = conv_wino_prepare(w, mb).
     chan_sums: optional float32 [B, conv_wino_sum_chunks(H, W), Cout]; not together with a residual."""
-    _require_cuda("conv_wino_cl", x, wprep, bias, residual, out, chan_sums)
     b, cin, h, w = x.shape
     if not conv_wino_ok((3, 3), 1, cin, cout) or mb not in (1, 2) or cout % (16 * mb) or wprep.numel() != 16 * cout * cin:
         raise RuntimeError("conv_wino_cl: unsupported shape %s -> %d (mb=%d)" % (tuple(x.shape), cout, mb))
-    if out is None:
-        out = empty_cl(b, cout, h, w, x.device)
-    elif tuple(out.shape) != (b, cout, h, w):
-        raise RuntimeError("conv_wino_cl: out has shape %s" % (tuple(out.shape),))
-    if residual is not None and tuple(residual.shape) != (b, cout, h, w):
-        raise RuntimeError("conv_wino_cl: residual has shape %s" % (tuple(residual.shape),))
-    if chan_sums is not None and (residual is not None or not chan_sums.is_contiguous() or chan_sums.dtype != torch.float32 or
-                                  tuple(chan_sums.shape) != (b, conv_wino_sum_chunks(h, w), cout)):
-        raise RuntimeError("conv_wino_cl: chan_sums must be contiguous float32 [B, conv_wino_sum_chunks(H, W), Cout], without a residual")
-    lib = _lib.load()
-    args = (x.data_ptr(), _cl("conv_wino_cl", x), wprep.data_ptr(), bias.data_ptr() if bias is not None else None,
-            residual.data_ptr() if residual is not None else None, _cl("conv_wino_cl", residual) if residual is not None else 0,
-            out.data_ptr(), _cl("conv_wino_cl", out), b, h, w, cin, cout, int(mb), int(act),
-            chan_sums.data_ptr() if chan_sums is not None else None)
-    fn = lib.smos_conv_wino_cl
-    if not profiling.enabled():                      # the hot path: no label, no span
-        dev = x.device
-        with _on(dev):
-            rc = fn(*args, _raw_stream(_dev_index(dev)))
-        if rc:
-            _lib.check(rc, "smos_conv_wino_cl")
-        return out
-    label = "conv_cl[%dx%dx%dx%d->%dx%dx%dk3x3%s]" % (b, cin, h, w, cout, h, w, "+res" if residual is not None else "")
-    with _on(x.device), profiling.span(label, "conv_wino"):
-        rc = fn(*args, _stream(x))
-    _lib.check(rc, "smos_conv_wino_cl")
-    if profiling._replay_label == label:
-        keep = (x, wprep, bias, residual, out, chan_sums)
-
-        def again(keep=keep):
-            with _on(keep[0].device), profiling.span(label, "conv_wino"):
-                _lib.check(fn(*args, _stream(keep[0])), "smos_conv_wino_cl")
-        profiling.offer_replay(label, again)
+    out, head = _conv_operands("conv_wino_cl", x, wprep, bias, cout, h, w, residual, out, chan_sums, conv_wino_sum_chunks)
+    args = head + (b, h, w, cin, cout, int(mb), int(act), chan_sums.data_ptr() if chan_sums is not None else None)
+    _conv_launch("smos_conv_wino_cl", "conv_wino", args, (x, wprep, bias, residual, out, chan_sums), x,
+                 lambda: _conv_label("conv_cl", x, cout, h, w, (3, 3), residual))
     return out
 
 
@@ -1590,31 +1546,51 @@ def conv_wino1d_prepare(w, mb):
 def conv_wino1d_cl(x, wprep, bias, act, cout, kernel, mb=2, out=None):
     """act(conv(x) + bias) (stride 1, "same" padding) for a 5x3 / 7x3 / 3x5 / 3x7 kernel on channels-last [B,C,H,W] views in
     one launch of the 1-D Winograd F(2, 3) kernel (csrc/conv_wino1d.hip).  wprep = conv_wino1d_prepare(w, mb)."""
-    _require_cuda("conv_wino1d_cl", x, wprep, bias, out)
     b, cin, h, w = x.shape
     kh, kw = kernel
     if not conv_wino1d_ok(kernel, 1, cin, cout) or mb not in (1, 2) or cout % (16 * mb) or wprep.numel() != 4 * max(kh, kw) * cout * cin:
         raise RuntimeError("conv_wino1d_cl: unsupported shape %s -> %d k%dx%d (mb=%d)" % (tuple(x.shape), cout, kh, kw, mb))
-    if out is None:
-        out = empty_cl(b, cout, h, w, x.device)
-    elif tuple(out.shape) != (b, cout, h, w):
-        raise RuntimeError("conv_wino1d_cl: out has shape %s" % (tuple(out.shape),))
-    lib = _lib.load()
-    label = "conv_cl[%dx%dx%dx%d->%dx%dx%dk%dx%d]" % (b, cin, h, w, cout, h, w, kh, kw) if profiling.enabled() else None
-    args = (x.data_ptr(), _cl("conv_wino1d_cl", x), wprep.data_ptr(), bias.data_ptr() if bias is not None else None,
-            out.data_ptr(), _cl("conv_wino1d_cl", out), b, h, w, cin, cout, kh, kw, int(mb), int(act))
-    fn = lib.smos_conv_wino1d_cl
-    with _on(x.device), profiling.span(label, "conv_wino1d"):
-        rc = fn(*args, _stream(x))
-    _lib.check(rc, "smos_conv_wino1d_cl")
-    if label is not None and profiling._replay_label == label:
-        keep = (x, wprep, bias, out)
-
-        def again(keep=keep):
-            with _on(keep[0].device), profiling.span(label, "conv_wino1d"):
-                _lib.check(fn(*args, _stream(keep[0])), "smos_conv_wino1d_cl")
-        profiling.offer_replay(label, again)
+    out, head = _conv_operands("conv_wino1d_cl", x, wprep, bias, cout, h, w, out=out)
+    args = head[:4] + head[6:] + (b, h, w, cin, cout, kh, kw, int(mb), int(act))      # this kernel takes no residual
+    _conv_launch("smos_conv_wino1d_cl", "conv_wino1d", args, (x, wprep, bias, out), x,
+                 lambda: _conv_label("conv_cl", x, cout, h, w, kernel))
     return out
+
+
+ConvSwitches = collections.namedtuple("ConvSwitches", "wino wino1d conv_rows conv_rows_mt", defaults=(True, True, 3, 1))
+
+
+def conv_route(cin, cout, kernel, stride, n_out_pixels, has_residual, has_sums, switches):
+    """(family, tile) of the fp32 kernel a conv layer runs on, from its shape alone -- the caller has settled that the own
+    kernels cover it (conv_cl_supported).  family "wino" / "wino1d" (tile = mb, 16-channel output blocks per wave) or "rows" /
+    "igemm" (tile = mt, 32-channel blocks); `switches`: anything with the A/B attributes of ConvSwitches (InferenceEngine has
+    them).  Plain numbers in, no library call: the table is pinned in tests/test_host_conv_route.py."""
+    if switches.wino and conv_wino_ok(kernel, stride, cin, cout):
+        return "wino", conv_wino_mb(cout)
+    if switches.wino1d and not has_residual and not has_sums and conv_wino1d_ok(kernel, stride, cin, cout):
+        return "wino1d", conv_wino_mb(cout)
+    mt = conv_mt(cout, n_out_pixels, has_residual)
+    if switches.conv_rows and mt <= switches.conv_rows_mt and conv_rows_ok(kernel, stride, cin, cout) and kernel[1] >= switches.conv_rows:
+        return "rows", mt
+    return "igemm", mt
+
+
+class ConvLayer:
+    """One folded conv weight w [Cout, Cin, KH, KW] with its operand-ordered copies, each made on first use: keyed by what
+    conv_route returns, plus "bf16".  Its owner keys it by id(w); it holds w, so that id stays w's.
+    ran_bf16: bf16 engines note here whether the layer's last launch ran on the bf16 kernel (None: not launched)."""
+    __slots__ = ("w", "packed", "ran_bf16")
+    _PREPARE = {"wino": conv_wino_prepare, "wino1d": conv_wino1d_prepare, "igemm": conv_prepare,
+                "rows": lambda w, mt: conv_prepare(w, mt, order="rows")}
+
+    def __init__(self, w):
+        self.w, self.packed, self.ran_bf16 = w, {}, None
+
+    def operand(self, key):
+        wp = self.packed.get(key)
+        if wp is None:
+            wp = self.packed[key] = conv_bf16_prepare(self.w) if key == "bf16" else self._PREPARE[key[0]](self.w, key[1])
+        return wp
 
 
 def empty_cl(b, c, h, w, device, zero=False):
