@@ -440,7 +440,7 @@ static int pointnet_scatter_launch(const float* xyzi, const float* coord, int32_
   // persistent waves: exactly as many blocks as are resident at once
   KernelSetup ks;
   if (int rc = kernel_setup(reinterpret_cast<const void*>(&pointnet_scatter), 0, kBlock, &ks, "pointnet_scatter")) return rc;
-  const int64_t resident = (int64_t)ks.per_cu * ks.cus;
+  const int64_t resident = conv_grid_cap((int64_t)ks.per_cu * ks.cus);      // (the test hook's cap: several trips per wave)
   const int64_t n_nt = (int64_t)a.S * ((N + kNt - 1) / kNt);
   SMOS_REQUIRE(n_nt < (1LL << 30), "pointnet_scatter: too many points for 32-bit tile indices");
   const int64_t want = (n_nt + 3) / 4;

@@ -410,8 +410,9 @@ extern "C" int smos_stem_gemm(const float* bev, const int32_t* row_cell, const i
     a.wprep[c] = wprep4[c];
     a.y[c] = y4[c];
   }
-  // one block per CU (120 KB of LDS); the kernel splits the work from the device-side row counts
-  const int at = cus < 1 ? 1 : cus;
+  // one block per CU (120 KB of LDS); the kernel splits the work from the device-side row counts (any grid gives the same
+  // bits: one accumulator per output block, fixed k order -- the test hook's cap makes a wave walk many units)
+  const int at = (int)conv_grid_cap(cus < 1 ? 1 : cus);
   hipLaunchKernelGGL(stem_gemm, dim3(at), dim3(kStemBlock), lds, (hipStream_t)stream, a);
   return check_launch("stem_gemm");
 }

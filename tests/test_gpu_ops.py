@@ -12,7 +12,7 @@ from streammos_amd import ops
 from streammos_amd.refapi import deep_point
 from streammos_amd.refapi.deformattn.functions import MSDeformAttnFunction
 from tests import cases
-from tests.util import check_inputs
+from tests.util import check_inputs, conv_grid_cap
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -1009,19 +1009,6 @@ def test_conv_wino1d_cl_against_float64(cin, cout, hw, kernel, mb, act):
     assert torch.equal(got2, got)                                                     # run-to-run identical, pitch-independent
 
 
-@pytest.fixture
-def conv_grid_cap():
-    """smos_debug_set_conv_grid_cap for the duration of a test: the persistent conv kernels launch at most `blocks` blocks, so a
-    block walks several work items on shapes that are still small enough for a float64 reference."""
-    from streammos_amd import _lib
-    lib = _lib.load()
-
-    def set_cap(blocks):
-        _lib.check(lib.smos_debug_set_conv_grid_cap(int(blocks)), "smos_debug_set_conv_grid_cap")
-    yield set_cap
-    lib.smos_debug_set_conv_grid_cap(0)
-
-
 _WINO_WALK_CASES = [
     # cin, cout, (h, w), mb, act, residual, batch, grid cap (0 = the device's own resident grid)
     (64, 64, (256, 256), 2, 1, False, 4, 0),        # VERDICT r3: 2048 items on 512 resident blocks (conv_2-like walk at full grid)
@@ -1034,7 +1021,7 @@ _WINO_WALK_CASES = [
 
 
 @pytest.mark.parametrize("cin,cout,hw,mb,act,with_res,b,cap", _WINO_WALK_CASES)
-def test_conv_wino_cl_persistent_walk_over_several_items(cin, cout, hw, mb, act, with_res, b, cap, conv_grid_cap):
+def test_conv_wino_cl_persistent_walk_over_several_items(cin, cout, hw, mb, act, with_res, b, cap):
     """The persistent multi-item walk of csrc/conv_wino.hip (next_item, the region prefetch across an item boundary, the
     epilogue between items, the cyclic weight-slice counter, conv_wino.hip:72-82,178-191,404-447): shapes with MORE work items
     than blocks, with the cout-tile / x / y / sample wraps all inside one block -- against conv2d in float64 (2e-5 of the range)
@@ -1048,9 +1035,8 @@ def test_conv_wino_cl_persistent_walk_over_several_items(cin, cout, hw, mb, act,
     wt = (torch.randn((cout, cin, 3, 3), generator=gen) * (2.0 / (cin * 9)) ** 0.5).to(DEV)
     bias = torch.randn(cout, generator=gen).to(DEV)
     items = b * ((h + 7) // 8) * ((w + 31) // 32) * (cout // (16 * mb))
-    conv_grid_cap(cap)
-    got = ops.conv_wino_cl(x, ops.conv_wino_prepare(wt, mb), bias, act, cout, mb=mb, residual=res)
-    conv_grid_cap(0)
+    with conv_grid_cap(cap):
+        got = ops.conv_wino_cl(x, ops.conv_wino_prepare(wt, mb), bias, act, cout, mb=mb, residual=res)
     want = F.conv2d(x.double(), wt.double(), bias.double(), 1, 1)
     if with_res:
         want = want + res.double()
@@ -1074,7 +1060,7 @@ def test_conv_wino_cl_persistent_walk_over_several_items(cin, cout, hw, mb, act,
     (48, 48, (70, 50), (3, 5), 1, 0, 2, 4),         # mb = 1, nct = 3, 3 chunks
     (16, 32, (33, 64), (5, 3), 2, 1, 2, 3),         # one chunk per item
 ])
-def test_conv_wino1d_cl_persistent_walk_over_several_items(cin, cout, hw, kernel, mb, act, b, cap, conv_grid_cap):
+def test_conv_wino1d_cl_persistent_walk_over_several_items(cin, cout, hw, kernel, mb, act, b, cap):
     """The same for csrc/conv_wino1d.hip (one block per CU; 16 L-rows x 32 S-columns x 16 mb couts per item)."""
     import torch.nn.functional as F
     gen = torch.Generator(device="cpu").manual_seed(103)
@@ -1082,9 +1068,8 @@ def test_conv_wino1d_cl_persistent_walk_over_several_items(cin, cout, hw, kernel
     x = torch.randn((b, cin) + hw, generator=gen).to(DEV).contiguous(memory_format=torch.channels_last)
     w = (torch.randn((cout, cin, kh, kw), generator=gen) / (kh * kw * cin) ** 0.5).to(DEV)
     bias = torch.randn(cout, generator=gen).to(DEV)
-    conv_grid_cap(cap)
-    got = ops.conv_wino1d_cl(x, ops.conv_wino1d_prepare(w, mb), bias, act, cout, kernel, mb=mb)
-    conv_grid_cap(0)
+    with conv_grid_cap(cap):
+        got = ops.conv_wino1d_cl(x, ops.conv_wino1d_prepare(w, mb), bias, act, cout, kernel, mb=mb)
     want = F.conv2d(x.double(), w.double(), bias.double(), 1, (kh // 2, kw // 2))
     want = want if act == 0 else (torch.relu(want) if act == 1 else F.leaky_relu(want, 0.01))
     scale = want.abs().max().item()
