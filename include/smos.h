@@ -169,37 +169,6 @@ int smos_box_vote(const float* pts, int64_t n, int64_t pt_stride, const uint8_t*
                   const float* boxes, int32_t K, uint32_t* counts, smos_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
- * Fused elementwise epilogues of the encoder (inference: BatchNorm scale folded into the conv weights on
- * the host, so every conv -> BN -> ReLU (-> add -> ReLU) chain of the reference collapses into one
- * pass).  All tensors float32; a "plane" is one contiguous (batch, channel) H*W slab, addressed as
- * base + b*stride_b + c*stride_c (element strides), which lets an output land inside a channel slice of a
- * concatenation buffer.
- */
-/* out = act(x + bias[c] (+ res)); act: 0 none, 1 ReLU, 2 LeakyReLU(0.01).  bias / res may be NULL.
- * Replaces BN+ReLU after a conv (networks/backbone.py:136-159, multi_view_encoder.py:460-497). */
-int smos_bias_act(const float* x, int64_t xs_b, int64_t xs_c, const float* bias, const float* res, int64_t rs_b,
-                  int64_t rs_c, float* out, int64_t os_b, int64_t os_c, int64_t B, int64_t C, int64_t HW,
-                  int32_t act, smos_stream_t stream);
-/* DownSample2D tail (networks/backbone.py:29-34): out = relu(a + bias[c] + maxpool3x3(p; stride, pad 1)).
- * a [B,C,Ho,Wo] and p [B,C,H,W] with full element strides (NCHW or channels-last); out planes contiguous. */
-int smos_downsample_epilogue(const float* a, const int64_t* a_stride, const float* p, const int64_t* p_stride,
-                             const float* bias, float* out, int64_t os_b, int64_t os_c, int64_t B, int64_t C,
-                             int64_t H, int64_t W, int32_t stride, smos_stream_t stream);
-/* BasicBlock tail with ChannelAtt (networks/backbone.py:87-102,151-159):
- * g = sigmoid(w2 * relu(w1 * mean_hw(y + bias) + b1) + b2); out = relu((y + bias) * g + xres).
- * w1 [Cr,C], w2 [C,Cr] (the 1x1 conv weights), sums_ws: device scratch of B*C floats. */
-int smos_channel_gate_residual(const float* y, int64_t ys_b, int64_t ys_c, const float* bias, const float* w1,
-                               const float* b1, const float* w2, const float* b2, const float* xres, int64_t rs_b,
-                               int64_t rs_c, float* out, int64_t os_b, int64_t os_c, float* sums_ws, int64_t B,
-                               int64_t C, int64_t Cr, int64_t HW, smos_stream_t stream);
-/* Decoder input (networks/multi_view_encoder.py:441-447): bilinear resize (align_corners=True) of up to three
- * NCHW maps to (Ho, Wo), concatenated along channels into out [B, sum C_i, Ho, Wo] (contiguous).
- * src[i]: device pointers (host array), per-source C/H/W and batch/channel strides (host arrays). */
-int smos_upsample_concat(const float* const* src, const int64_t* src_c, const int64_t* src_h, const int64_t* src_w,
-                         const int64_t* src_sb, const int64_t* src_sc, int32_t n_src, float* out, int64_t B,
-                         int64_t Ho, int64_t Wo, smos_stream_t stream);
-
-/* --------------------------------------------------------------------------------------------
  * Fused point-side kernels of the inference engine (csrc/point_fused.hip).  Scatter targets are
  * channels-last and zero-filled by the caller; features are assumed >= 0 (post-ReLU), as on every call
  * site of the model.
@@ -397,17 +366,6 @@ int smos_pointnet_scatter_rows_live(const float* xyzi, const float* coord, int32
                                     const float* w2, const float* b2, float* rows, const int32_t* row_of, float* pts_out,
                                     int64_t po_b, int64_t po_n, int64_t B, int64_t T, int64_t N, int64_t H, int64_t W, int32_t cin,
                                     int32_t cmid, int32_t cout, const int32_t* n_live, smos_stream_t stream);
-/* BilinearSample (networks/backbone.py:453-475) of grid [B,C,Hg,Wg] (element strides grid_stride[4]) at
- * gcoord*gscale, fused with VoxelMaxPool of the result into out [B,Ho,Wo,C] (channels-last) at
- * int(scoord*sscale) (networks/multi_view_encoder.py:395-404,410-419).  out may be NULL (gather only);
- * pts_out (optional) receives the gathered features as rows pts_out[b*po_b + n*po_n + c]. C % 32 == 0. */
-int smos_gather_scatter(const float* grid, const int64_t* grid_stride, const float* gcoord, int32_t Kg,
-                        const float* gscale, const float* scoord, int32_t Ks, const float* sscale, float* out,
-                        float* pts_out, int64_t po_b, int64_t po_n, int64_t B, int64_t C, int64_t Hg, int64_t Wg,
-                        int64_t N, int64_t Ho, int64_t Wo, smos_stream_t stream);
-/* channels-last [B, HW, C] -> NCHW planes dst[b*ds_b + c*ds_c + p] (a channel slice of a larger buffer). */
-int smos_nhwc_to_nchw(const float* src, float* dst, int64_t ds_b, int64_t ds_c, int64_t B, int64_t C, int64_t HW,
-                      smos_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * Device-side validation preprocessing (csrc/preprocess.hip): what DataloadVal does with
@@ -512,7 +470,10 @@ int smos_upsample_concat_cl(const float* const* src, const int64_t* src_c, const
 int smos_downsample_pool_branch(const float* x, int64_t x_pitch, const float* wpairs, const float* a, int64_t a_pitch,
                                 const float* bias, float* out, int64_t out_pitch, int64_t B, int64_t H, int64_t W, int64_t Cin,
                                 int64_t Cout, int32_t stride, smos_stream_t stream);
-/* smos_gather_scatter with a channels-last source grid [B,Hg,Wg,*] and target [B,Ho,Wo,*]; C is 32 or 64. */
+/* BilinearSample (networks/backbone.py:453-475) of the channels-last grid [B,Hg,Wg,*] (pixel pitch grid_pitch, C channels read)
+ * at gcoord*gscale, fused with VoxelMaxPool of the result into the zero-filled channels-last out [B,Ho,Wo,*] (pixel pitch
+ * out_pitch) at int(scoord*sscale) (networks/multi_view_encoder.py:395-404,410-419).  out may be NULL (gather only); pts_out
+ * (optional) receives the gathered features as rows pts_out[b*po_b + n*po_n + c].  C is 32 or 64. */
 int smos_gather_scatter_cl(const float* grid, int64_t grid_pitch, const float* gcoord, int32_t Kg, const float* gscale,
                            const float* scoord, int32_t Ks, const float* sscale, float* out, int64_t out_pitch, float* pts_out,
                            int64_t po_b, int64_t po_n, int64_t B, int64_t C, int64_t Hg, int64_t Wg, int64_t N, int64_t Ho,

@@ -33,9 +33,6 @@ SIGNATURES = {
     "smos_dbscan_work_bytes": [i64],
     "smos_dbscan": [vp, i64, i64, ctypes.c_double, i32, vp, vp, i64, i32, vp],
     "smos_box_vote": [vp, i64, i64, vp, c_f64p, vp, i32, vp, vp],
-    "smos_bias_act": [vp, i64, i64, vp, vp, i64, i64, vp, i64, i64, i64, i64, i64, i32, vp],
-    "smos_downsample_epilogue": [vp, c_i64p, vp, c_i64p, vp, vp, i64, i64, i64, i64, i64, i64, i32, vp],
-    "smos_channel_gate_residual": [vp, i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i64, vp],
     "smos_pointnet_scatter": [vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, i32, i32, vp],
     "smos_stem_scan_state_words": [i64],
     "smos_stem_mark": [vp, i32, i64, i64, i64, i64, i64, vp, vp, vp],
@@ -72,8 +69,6 @@ SIGNATURES = {
     "smos_upconv_ypass": [vp, i64, vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, i32, vp],
     "smos_upconv_xy_ok": [i64, i64],
     "smos_upconv_xy": [vp, i64, vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i64, i64, i32, vp],
-    "smos_gather_scatter": [vp, c_i64p, vp, i32, c_f32p, vp, i32, c_f32p, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp],
-    "smos_nhwc_to_nchw": [vp, vp, i64, i64, i64, i64, i64, vp],
     "smos_prep_transform_mask": [vp, i64, c_f64p, c_f64p, vp, vp, vp],
     "smos_prep_emit": [vp, vp, vp, i64, i32, i32, i64, i32, c_f32p, c_f32p, c_f64p, c_i64p, c_f64p, vp, vp, vp, vp],
     "smos_prep_unpad_labels": [vp, i64, vp, vp, i64, vp, vp],
@@ -86,7 +81,6 @@ SIGNATURES = {
     "smos_downsample_pool_branch": [vp, i64, vp, vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, i32, vp],
     "smos_gather_scatter_cl_view": [vp, i64, vp, i32, i64, c_f32p, vp, i32, i64, c_f32p, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp],
     "smos_gather_scatter_cl_live": [vp, i64, vp, i32, c_f32p, vp, i32, c_f32p, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp],
-    "smos_upsample_concat": [ctypes.POINTER(vp), c_i64p, c_i64p, c_i64p, c_i64p, c_i64p, i32, vp, i64, i64, i64, vp],
     "smos_label_words": [vp, i64, i32, vp, vp, vp, i32, vp, vp],
     "smos_label_count_voted": [vp, i64, vp, vp, vp, i32, vp, vp],
 }

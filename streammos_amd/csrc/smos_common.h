@@ -65,9 +65,6 @@ __device__ __forceinline__ double pose_row_f64(const double* m, double x, double
   return __dadd_rn(__fma_rn(m[2], z, __fma_rn(m[1], y, __dmul_rn(m[0], x))), m[3]);
 }
 
-struct Dims4 {
-  int64_t v[4];
-};
 struct Scale4 {
   float v[4];
 };

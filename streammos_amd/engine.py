@@ -4,12 +4,18 @@
 tensors; on a GPU in eval mode they hand over to this engine, which computes the same function
 (models/StreamMOS.py:86-113, networks/multi_view_encoder.py:390-458) with far fewer passes over HBM:
 
-* BatchNorm is folded into the preceding conv's weights once (float64 on the host); what is left of
-  every conv -> BN -> ReLU (-> add -> ReLU) chain is one fused epilogue kernel (csrc/epilogue.hip);
+* every feature map is channels-last, which is also the layout of the scatters and of the attention tokens: nothing is transposed;
+* BatchNorm is folded into the preceding conv's weights once (float64 on the host), and every conv -> BN -> ReLU (-> add -> ReLU)
+  chain is one launch of an own convolution kernel with the epilogue fused (csrc/conv_wino.hip, conv_wino1d.hip, conv_igemm.hip,
+  conv_rows.hip; opt-in bf16: conv_bf16.hip); MIOpen is only the fallback for shapes those kernels do not cover (``_conv``);
+* the first BEV stage runs on the occupied cells only (csrc/stem.hip): the dense input grid is never built;
 * concatenations never run: producers write straight into channel slices of the destination buffer
   (conv epilogues, scatters and gathers all take output strides);
-* the three bilinear resizes + ``torch.cat`` in front of ``conv_1`` are one kernel;
-* the convs themselves stay on PyTorch-ROCm / MIOpen (NCHW Winograd kernels).
+* ``conv_1`` takes the two coarser maps as tap GEMMs at source resolution (csrc/upconv.hip) instead of three bilinear
+  resizes + ``torch.cat``;
+* temporal fusion is the deformable-attention sampler plus one fused kernel per layer (csrc/tfusion.hip);
+* ``encode`` holds everything that does not depend on the previous frame, ``decode_memory`` the part that is serial across
+  frames and ``decode_heads`` the rest, so the streaming runner can overlap them.
 
 The engine holds *copies* of the folded weights: it is rebuilt whenever the module's parameters may have
 changed (``load_state_dict``, ``.to()``, ``.train()``), see ``AttNet._engine_for``.
@@ -55,18 +61,16 @@ CONV_PRECISIONS = ("fp32", "bf16")
 
 class InferenceEngine:
     def __init__(self, net, layout="cl", conv_precision="fp32"):
-        """layout "cl": every feature map channels-last (default; fastest under MIOpen's solver search and the natural
-        layout of the scatters and of the attention tokens); "nchw": the first version of the engine, kept for A/B.
-        conv_precision "fp32" (default: exact fp32 everywhere) or "bf16" (opt-in, channels-last only): every layer that goes
+        """layout: "cl" (every feature map channels-last) is the only layout; the argument and the attribute remain because
+        AttNet.engine_layout and bench.py name it.  The first-generation NCHW / MIOpen engine was removed: any other value raises.
+        conv_precision "fp32" (default: exact fp32 everywhere) or "bf16" (opt-in): every layer that goes
         through _conv -- the BasicBlock, Unbalance and DownSample2D convs and the decoder's conv_1a / conv_2 -- runs on the
         bf16 matrix-core kernel (csrc/conv_bf16.hip: bf16-rounded weights and activations, fp32 sums and epilogue); a layer
         the kernel does not cover stays on the fp32 path and is counted (conv_precision_stats)."""
-        if layout not in ("cl", "nchw"):
-            raise ValueError("layout must be 'cl' or 'nchw'")
+        if layout != "cl":        # before anything touches net
+            raise ValueError("layout=%r: the NCHW engine was removed, 'cl' (channels-last) is the only layout" % (layout,))
         if conv_precision not in CONV_PRECISIONS:
             raise ValueError("conv_precision must be one of %s, got %r" % (CONV_PRECISIONS, conv_precision))
-        if conv_precision != "fp32" and layout != "cl":
-            raise ValueError("conv_precision=%r needs layout='cl'" % (conv_precision,))
         self.layout = layout
         self.conv_precision = conv_precision
         self._bf16 = conv_precision == "bf16"
@@ -165,17 +169,17 @@ class InferenceEngine:
                 self.refine_w = ops.point_head_prepare(*self.refine)
         except RuntimeError:
             self.head_w = self.refine_w = None
-        if layout == "cl":
-            for blocks in (self.header_bev, self.header_rv, self.res1_bev, self.res1_rv, self.res2):
-                for p in blocks:
-                    for k in ("wa", "wp", "wb", "wc", "w1", "w2"):
-                        if hasattr(p, k):
-                            setattr(p, k, _cl_w(getattr(p, k)))
-            self.conv_1a = _cl_w(self.conv_1a)
-            self.aux_split = [(_cl_w(w), b) for w, b in self.aux_split]
-            self.conv_1 = (_cl_w(self.conv_1[0]), self.conv_1[1])
-            self.conv_2 = (_cl_w(self.conv_2[0]), self.conv_2[1])
-            self.aux = (_cl_w(self.aux[0]), self.aux[1], self.aux[2])
+        # the folded weights in the memory format of the maps
+        for blocks in (self.header_bev, self.header_rv, self.res1_bev, self.res1_rv, self.res2):
+            for p in blocks:
+                for k in ("wa", "wp", "wb", "wc", "w1", "w2"):
+                    if hasattr(p, k):
+                        setattr(p, k, _cl_w(getattr(p, k)))
+        self.conv_1a = _cl_w(self.conv_1a)
+        self.aux_split = [(_cl_w(w), b) for w, b in self.aux_split]
+        self.conv_1 = (_cl_w(self.conv_1[0]), self.conv_1[1])
+        self.conv_2 = (_cl_w(self.conv_2[0]), self.conv_2[1])
+        self.aux = (_cl_w(self.aux[0]), self.aux[1], self.aux[2])
         # every 2-D convolution of the channels-last engine runs on the library's own implicit-GEMM kernel with the
         # epilogue fused (csrc/conv_igemm.hip).  SMOS_OWN_CONV=0 falls back to MIOpen convs + separate epilogue passes
         # (kept for A/B runs; tools/ubench_conv.py compares the two per layer).
@@ -226,32 +230,6 @@ class InferenceEngine:
         raise RuntimeError("InferenceEngine: unexpected module %s" % type(m).__name__)
 
     # ---- blocks ---------------------------------------------------------------------------
-    def _run_block(self, x, p, out=None):
-        if p.kind == "down":
-            if x.stride(1) == 1 and x.shape[1] > 1:       # channels-last input (the scatter target of stage 0)
-                a = F.conv2d(x, p.wa.contiguous(memory_format=torch.channels_last), None, p.stride, 1)
-                q = F.conv2d(x, p.wp.contiguous(memory_format=torch.channels_last))
-                dst = out if out is not None else torch.empty(a.shape, dtype=a.dtype, device=a.device)
-                return ops.downsample_epilogue(a, q, p.bias, p.stride, out=dst)
-            a = F.conv2d(x, p.wa, None, p.stride, 1)
-            q = F.conv2d(x, p.wp)
-            return ops.downsample_epilogue(a, q, p.bias, p.stride, out=out if out is not None else a)
-        if p.kind == "unbalance":
-            b, c, h, w = x.shape
-            both = torch.empty((b, 2 * c, h, w), dtype=x.dtype, device=x.device)
-            ops.bias_act(F.conv2d(x, p.wa, None, 1, p.pa), p.ba, RELU, out=both[:, :c])
-            ops.bias_act(F.conv2d(x, p.wb, None, 1, p.pb), p.bb, RELU, out=both[:, c:])
-            y = F.conv2d(both, p.wc, None, 1, 1)
-            return ops.bias_act(y, p.bc, RELU, out=out if out is not None else y, residual=x)
-        y = F.conv2d(x, p.w1, None, 1, 1)
-        ops.bias_act(y, p.b1, RELU, out=y)
-        y2 = F.conv2d(y, p.w2, None, 1, 1)
-        dst = out if out is not None else y2
-        if p.att:
-            return ops.channel_gate_residual(y2, p.b2, p.cw1, p.cb1, p.cw2, p.cb2, x, self._block_ws(p, y2.shape[0] * y2.shape[1]),
-                                             out=dst)
-        return ops.bias_act(y2, p.b2, RELU, out=dst, residual=x)
-
     @staticmethod
     def _linear_relu(x, wb):
         """relu(x @ W^T + b) for a folded 1x1 conv (W [Cout, Cin, 1, 1]) on point rows; the bias + ReLU epilogue
@@ -297,28 +275,6 @@ class InferenceEngine:
             ws = table[key] = torch.zeros(n_floats, dtype=torch.float32, device=self.device)
         return ws
 
-    def _run_stage(self, x, blocks, out=None):
-        for i, p in enumerate(blocks):
-            x = self._run_block(x, p, out if i == len(blocks) - 1 else None)
-        return x
-
-    def _cross_view(self, cat_buf, c, bev_xy, sphere, rv_blocks, rv_hw, scale, point_rows=None):
-        """cat_buf[:, :c] holds the BEV feature; fills cat_buf[:, c:] with the range-view branch scattered back
-        (multi_view_encoder.py:395-405 / :410-420).  B2P gather + P2R scatter and R2P gather + P2B scatter are
-        one kernel each (csrc/point_fused.hip); the channels-last scatter targets are transposed into the NCHW
-        maps the convs want.  point_rows (optional [B,N,c] row view) receives the R2P point features."""
-        bev = cat_buf[:, :c]
-        b = bev.shape[0]
-        dev = bev.device
-        rv_cl = torch.zeros((b,) + rv_hw + (c,), dtype=torch.float32, device=dev)
-        ops.gather_scatter(bev, bev_xy, scale, sphere, scale, out=rv_cl)
-        rv = ops.nhwc_to_nchw(rv_cl, torch.empty((b, c) + rv_hw, dtype=torch.float32, device=dev))
-        rv = self._run_stage(rv, rv_blocks)
-        back = cat_buf[:, c:]
-        back_cl = torch.zeros((b,) + tuple(back.shape[2:]) + (c,), dtype=torch.float32, device=dev)
-        ops.gather_scatter(rv, sphere, scale, bev_xy, scale, out=back_cl, pts_out=point_rows)
-        ops.nhwc_to_nchw(back_cl, back)
-
     @staticmethod
     def _add_norm(a, b, norm, c):
         """LayerNorm(a + b) in one pass (csrc/epilogue.hip) for the token widths that kernel is built for."""
@@ -326,7 +282,7 @@ class InferenceEngine:
             return ops.add_layer_norm(a.contiguous(), b.contiguous(), norm[0], norm[1], norm[2] if len(norm) > 2 else 1e-5)
         return F.layer_norm(a + b, (c,), norm[0], norm[1], norm[2] if len(norm) > 2 else 1e-5)
 
-    def _temporal_fusion(self, x2, memory, channels_last=False):
+    def _temporal_fusion(self, x2, memory):
         """DeformAttnModule (multi_view_encoder.py:426-439, 245-321): the memory stream queries the current map."""
         b, c, hh, ww = x2.shape
         dev = x2.device
@@ -345,7 +301,7 @@ class InferenceEngine:
         else:
             query = memory.permute(0, 2, 3, 1).reshape(b, hh * ww, c)
         lq = hh * ww
-        if self.tfusion and self._tf_ok and channels_last and c == 128:
+        if self.tfusion and self._tf_ok and c == 128:
             # five launches: projections | (sampler, layer) x 2
             query = query if query.is_contiguous() else query.contiguous()
             jobs = [(src, L.wv_stream, L.value[1]) for L in self.layers] + [(query, self.layers[0].wq_stream, self.layers[0].qproj[1])]
@@ -372,9 +328,7 @@ class InferenceEngine:
             query = self._add_norm(query, F.linear(sampled, *L.out), L.norm1, c)
             ffn = F.linear(self._linear_relu(query.view(b * lq, c), L.lin1).view(b, lq, -1), *L.lin2)
             query = self._add_norm(query, ffn, L.norm2, c)
-        if channels_last:
-            return query.contiguous().view(b, hh, ww, c).permute(0, 3, 1, 2)
-        return query.transpose(1, 2).reshape(b, c, hh, ww).contiguous()
+        return query.contiguous().view(b, hh, ww, c).permute(0, 3, 1, 2)
 
     # ---- the network ------------------------------------------------------------------------
     @torch.no_grad()
@@ -385,16 +339,14 @@ class InferenceEngine:
         """MIOpen solver search (measure every applicable solver once per conv shape, then reuse the fastest) --
         what the reference's own test scripts switch on (test_StreamMOS.py:20-23).  +7 % scans/s at the val shape;
         scoped to the engine's calls instead of flipping the process-wide flag."""
-        if self.own_conv and self.layout == "cl":
+        if self.own_conv:
             return ops._NO_GUARD          # every convolution of this engine is an own kernel: nothing for MIOpen to search
         return torch.backends.cudnn.flags(enabled=True, benchmark=self.miopen_search)
 
     def encode(self, point_feat, pcds_coord, pcds_sphere_coord, n_live=None):
         """n_live (device int32 tensor, runner only): see decode(); the point rows of the padding tail are not produced."""
         with torch.no_grad(), self._conv_flags():
-            if self.layout == "cl":
-                return self._encode_cl(point_feat, pcds_coord, pcds_sphere_coord, n_live)
-            return self._encode(point_feat, pcds_coord, pcds_sphere_coord)
+            return self._encode_cl(point_feat, pcds_coord, pcds_sphere_coord, n_live)
 
     def decode(self, enc, memory=None, want_aux=True, n_live=None):
         """want_aux=False: the three BEV aux maps (training-time supervision heads, models/StreamMOS.py:106-111) are not
@@ -408,19 +360,14 @@ class InferenceEngine:
         """The only part that is serial across frames: third BEV stage + deformable-attention fusion with the previous
         frame's memory.  Returns the new memory (= the fused 1/8-resolution map)."""
         with torch.no_grad(), self._conv_flags():
-            if self.layout == "cl":
-                x2 = enc["x2"] if "x2" in enc else self._stage_cl(enc["x1cat"], self.res2)
-                return self._temporal_fusion(x2, memory, channels_last=True)
-            return self._temporal_fusion(enc["x2"], memory)
+            return self._temporal_fusion(self._stage_cl(enc["x1cat"], self.res2), memory)
 
     def decode_heads(self, enc, x2, want_aux=True, n_live=None):
         """Decoder convs, aux heads, bev->point gather and the point heads; nothing here feeds the next frame."""
         with torch.no_grad(), self._conv_flags():
-            if self.layout == "cl":
-                return self._decode_cl(enc, x2, want_aux, n_live)
-            return self._decode(enc, x2)
+            return self._decode_cl(enc, x2, want_aux, n_live)
 
-    # ---- channels-last path -----------------------------------------------------------------------
+    # ---- convolutions and blocks ------------------------------------------------------------------
     def conv_precision_stats(self):
         """bf16 mode: {"bf16": layers whose last launch ran on the bf16 kernel, "fallback": layers that stayed on the fp32
         path (shapes the bf16 kernel does not cover)}; one entry per layer, so after a step these are that step's counts.
@@ -699,51 +646,3 @@ class InferenceEngine:
         bev_feat = self._conv(y, self.conv_2[0], self.conv_2[1], LEAKY)
         ops.gather_scatter_cl(bev_feat, bev_xy, self.grid2point_scale, pts_out=fuse[:, :, o1:o2], n_live=n_live)
         return self._point_heads(fuse, aux, k, x2, n_live)
-
-    def _encode(self, point_feat, pcds_coord, pcds_sphere_coord):
-        """Everything that does NOT depend on the previous frame: point MLP + input scatter, the three BEV stages
-        and both cross-view cascades (multi_view_encoder.py:393-423).  The recurrent memory only enters in
-        ``decode``, so the encoder of frame t+1 may run while frame t is still being decoded (StreamRunner pipeline)."""
-        bs, t, cin, n, _ = point_feat.shape
-        dev = point_feat.device
-        bev_xy = pcds_coord[:, 0, :, :2, 0].contiguous()
-        sphere = pcds_sphere_coord[:, 0, :, :, 0].contiguous()
-
-        # point_pre + input scatter in one kernel; the BEV grid is channels-last, the t = 0 point features go
-        # straight into the point-wise fusion buffer [pts(t=0) | bev gather | range-view gather] (point rows)
-        cpt = self.pp2[0].shape[0]
-        hb, wb = self.bev_hw
-        c_dec, c1 = self.conv_2[0].shape[0], self.res1_bev[-1].w2.shape[0]
-        o1, o2 = cpt, cpt + c_dec
-        fuse = torch.empty((bs, n, cpt + c_dec + c1), dtype=torch.float32, device=dev)
-        bev_cl = torch.empty((bs, hb, wb, t * cpt), dtype=torch.float32, device=dev)
-        ops.pointnet_scatter(point_feat.float(), pcds_coord, self.pp1[0], self.pp1[1], self.pp2[0], self.pp2[1], bev_cl,
-                             pts_out=fuse[:, :, :o1], zero_fill=True)
-        bev = bev_cl.permute(0, 3, 1, 2)            # logical NCHW view of the channels-last buffer
-
-        c0 = self.header_bev[-1].w2.shape[0]
-        x0cat = torch.empty((bs, 2 * c0, hb // 2, wb // 2), dtype=torch.float32, device=dev)
-        self._run_stage(bev, self.header_bev, out=x0cat[:, :c0])
-        self._cross_view(x0cat, c0, bev_xy, sphere, self.header_rv, (32, 1024), (0.5, 0.5))
-
-        x1cat = torch.empty((bs, 2 * c1, hb // 4, wb // 4), dtype=torch.float32, device=dev)
-        self._run_stage(x0cat, self.res1_bev, out=x1cat[:, :c1])
-        self._cross_view(x1cat, c1, bev_xy, sphere, self.res1_rv, (16, 512), (0.25, 0.25), point_rows=fuse[:, :, o2:])
-
-        x2 = self._run_stage(x1cat, self.res2)
-        return {"x0cat": x0cat, "x1cat": x1cat, "x2": x2, "fuse": fuse, "bev_xy": bev_xy, "o1": o1, "o2": o2}
-
-    def _decode(self, enc, x2):
-        """Decoder and point heads of the NCHW engine (multi_view_encoder.py:441-456, models/StreamMOS.py:105-113)."""
-        x0cat, x1cat, fuse, bev_xy, o1, o2 = enc["x0cat"], enc["x1cat"], enc["fuse"], enc["bev_xy"], enc["o1"], enc["o2"]
-
-        dec_in = ops.upsample_concat([x0cat, x1cat, x2], tuple(x0cat.shape[2:]))
-        y = F.conv2d(dec_in, self.conv_1[0], None, 1, 1)
-        ops.bias_act(y, self.conv_1[1], LEAKY, out=y)
-        bev_feat = F.conv2d(y, self.conv_2[0], None, 1, 1)
-        ops.bias_act(bev_feat, self.conv_2[1], LEAKY, out=bev_feat)
-        aux = F.conv2d(dec_in, self.aux[0], self.aux[1])
-        k = self.aux[2]
-
-        ops.gather_scatter(bev_feat, bev_xy, self.grid2point_scale, pts_out=fuse[:, :, o1:o2])
-        return self._point_heads(fuse, aux, k, x2)

@@ -393,88 +393,9 @@ def voted_label_counts(voted, gt, gt_map, counts, words=None):
 
 
 # ---------------------------------------------------------------------------------------------
-# fused encoder epilogues (inference engine)
+# activation codes of the fused epilogues (inference engine)
 # ---------------------------------------------------------------------------------------------
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
-
-
-def _planes(name, t):
-    """(batch stride, channel stride, H*W) of a 4-D tensor whose (H, W) planes are contiguous."""
-    if t.dim() != 4 or t.stride(3) != 1 or t.stride(2) != t.shape[3]:
-        raise RuntimeError("%s: expected contiguous (H, W) planes, got shape %s strides %s" % (name, tuple(t.shape), t.stride()))
-    return t.stride(0), t.stride(1), t.shape[2] * t.shape[3]
-
-
-def bias_act(x, bias, act, out=None, residual=None):
-    """out = act(x + bias[c] (+ residual)); x, residual, out: [B,C,H,W] with contiguous planes (out may be a
-    channel slice of a larger buffer, or x itself)."""
-    _require_cuda("bias_act", x, bias, out, residual)
-    if out is None:
-        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
-    xb, xc, hw = _planes("bias_act", x)
-    ob, oc, _ = _planes("bias_act", out)
-    rb = rc = 0
-    if residual is not None:
-        rb, rc, _ = _planes("bias_act", residual)
-    lib = _lib.load()
-    with _on(x.device):
-        rc_ = lib.smos_bias_act(x.data_ptr(), xb, xc, bias.data_ptr() if bias is not None else None,
-                                residual.data_ptr() if residual is not None else None, rb, rc, out.data_ptr(), ob, oc,
-                                x.shape[0], x.shape[1], hw, act, _stream(x))
-    _lib.check(rc_, "smos_bias_act")
-    return out
-
-
-def downsample_epilogue(a, p, bias, stride, out=None):
-    """relu(a + bias[c] + maxpool3x3(p, stride, pad 1)); a [B,C,Ho,Wo], p [B,C,H,W] any strides."""
-    _require_cuda("downsample_epilogue", a, p, bias, out)
-    if out is None:
-        out = torch.empty(a.shape, dtype=a.dtype, device=a.device)
-    ob, oc, _ = _planes("downsample_epilogue", out)
-    lib = _lib.load()
-    with _on(a.device):
-        rc = lib.smos_downsample_epilogue(a.data_ptr(), _lib.i64_array(a.stride()), p.data_ptr(), _lib.i64_array(p.stride()),
-                                          bias.data_ptr(), out.data_ptr(), ob, oc, p.shape[0], p.shape[1], p.shape[2],
-                                          p.shape[3], stride, _stream(a))
-    _lib.check(rc, "smos_downsample_epilogue")
-    return out
-
-
-def channel_gate_residual(y, bias, w1, b1, w2, b2, xres, sums_ws, out=None):
-    _require_cuda("channel_gate_residual", y, bias, w1, b1, w2, b2, xres, sums_ws, out)
-    if out is None:
-        out = torch.empty(y.shape, dtype=y.dtype, device=y.device)
-    yb, yc, hw = _planes("channel_gate_residual", y)
-    rb, rc, _ = _planes("channel_gate_residual", xres)
-    ob, oc, _ = _planes("channel_gate_residual", out)
-    lib = _lib.load()
-    with _on(y.device):
-        rc_ = lib.smos_channel_gate_residual(y.data_ptr(), yb, yc, bias.data_ptr(), w1.data_ptr(), b1.data_ptr(),
-                                             w2.data_ptr(), b2.data_ptr(), xres.data_ptr(), rb, rc, out.data_ptr(), ob, oc,
-                                             sums_ws.data_ptr(), y.shape[0], y.shape[1], w1.shape[0], hw, _stream(y))
-    _lib.check(rc_, "smos_channel_gate_residual")
-    return out
-
-
-def upsample_concat(sources, size, out=None):
-    """Bilinear (align_corners=True) resize of up to three [B,C_i,H_i,W_i] maps to `size`, concatenated along C."""
-    import ctypes
-    _require_cuda("upsample_concat", *sources)
-    b = sources[0].shape[0]
-    ctot = sum(s.shape[1] for s in sources)
-    if out is None:
-        out = torch.empty((b, ctot, size[0], size[1]), dtype=torch.float32, device=sources[0].device)
-    strides = [_planes("upsample_concat", s) for s in sources]
-    ptrs = (ctypes.c_void_p * len(sources))(*[s.data_ptr() for s in sources])
-    lib = _lib.load()
-    with _on(out.device):
-        rc = lib.smos_upsample_concat(ptrs, _lib.i64_array([s.shape[1] for s in sources]),
-                                      _lib.i64_array([s.shape[2] for s in sources]),
-                                      _lib.i64_array([s.shape[3] for s in sources]),
-                                      _lib.i64_array([st[0] for st in strides]), _lib.i64_array([st[1] for st in strides]),
-                                      len(sources), out.data_ptr(), b, size[0], size[1], _stream(out))
-    _lib.check(rc, "smos_upsample_concat")
-    return out
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1468,46 +1389,6 @@ def sparse_downsample(src, plan, wprep, bias, compact, out=None):
             _lib.check(lib.smos_stem_epilogue(y_ptrs, plan.meta.data_ptr(), plan.row_of.data_ptr(), bias.data_ptr(), out.data_ptr(),
                                               _cl("sparse_downsample", out), b, h, w, cout, st), "smos_stem_epilogue")
     return out
-
-
-def gather_scatter(grid, gcoord, gscale, scoord=None, sscale=None, out=None, pts_out=None):
-    """grid [B,C,Hg,Wg] any strides; gcoord / scoord [B,N,K] contiguous; out [B,Ho,Wo,C] zero-filled
-    channels-last (or None); pts_out [B,N,C] rows (or None)."""
-    _require_cuda("gather_scatter", grid, gcoord, scoord, out, pts_out)
-    b, c, hg, wg = grid.shape
-    n, kg = gcoord.shape[1], gcoord.shape[2]
-    ho = wo = ks = 0
-    if out is not None:
-        if not out.is_contiguous() or out.shape[3] != c:
-            raise RuntimeError("gather_scatter: out must be contiguous channels-last [B,Ho,Wo,C]")
-        ho, wo, ks = out.shape[1], out.shape[2], scoord.shape[2]
-    po_b = po_n = 0
-    if pts_out is not None:
-        po_b, po_n = _rows("gather_scatter", pts_out, c)
-    lib = _lib.load()
-    label = "gather_scatter[%dx%dx%dx%d->%d->%dx%d]" % (b, c, hg, wg, n, ho, wo)
-    with _on(grid.device), profiling.span(label):
-        rc = lib.smos_gather_scatter(grid.data_ptr(), _lib.i64_array(grid.stride()), gcoord.data_ptr(), kg,
-                                     _lib.f32_array(gscale), scoord.data_ptr() if out is not None else None, ks,
-                                     _lib.f32_array(sscale) if out is not None else None,
-                                     out.data_ptr() if out is not None else None,
-                                     pts_out.data_ptr() if pts_out is not None else None, po_b, po_n, b, c, hg, wg, n, ho, wo,
-                                     _stream(grid))
-    _lib.check(rc, "smos_gather_scatter")
-
-
-def nhwc_to_nchw(src, dst):
-    """src [B,H,W,C] contiguous -> dst [B,C,H,W] view with contiguous planes (e.g. a channel slice)."""
-    _require_cuda("nhwc_to_nchw", src, dst)
-    b, h, w, c = src.shape
-    db, dc, hw = _planes("nhwc_to_nchw", dst)
-    if not src.is_contiguous() or tuple(dst.shape) != (b, c, h, w):
-        raise RuntimeError("nhwc_to_nchw: shape mismatch %s -> %s" % (tuple(src.shape), tuple(dst.shape)))
-    lib = _lib.load()
-    with _on(src.device):
-        rc = lib.smos_nhwc_to_nchw(src.data_ptr(), dst.data_ptr(), db, dc, b, c, hw, _stream(src))
-    _lib.check(rc, "smos_nhwc_to_nchw")
-    return dst
 
 
 # ---------------------------------------------------------------------------------------------

@@ -37,7 +37,7 @@ class AttNet(nn.Module):
         self.point_feat_out_channels = pModel.point_feat_out_channels
         self.build_network()
         self.fast_inference = True      # eval-mode GPU inference runs the fused engine (streammos_amd/engine.py)
-        self.engine_layout = "cl"       # "cl" (channels-last, default) or "nchw"
+        self.engine_layout = "cl"       # "cl" (channels-last): the only layout, the NCHW engine was removed
         self.engine_conv_precision = "fp32"     # "fp32" (default, exact) or "bf16" (opt-in bf16 matrix-core convolutions)
         self.engine_miopen_search = True
         self._engine = None

@@ -421,44 +421,6 @@ def test_pointnet_scatter_run_boundaries_at_cell_zero():
     assert want[:, :, 0, 0].max().item() > 0
 
 
-@pytest.mark.parametrize("c,hw_g,hw_o,sg,ss", [(32, (64, 64), (8, 256), (0.5, 0.5), (0.5, 0.5)),
-                                              (64, (16, 128), (32, 32), (0.25, 0.25), (0.25, 0.25))])
-def test_gather_scatter_against_unfused_ops(c, hw_g, hw_o, sg, ss):
-    gen = torch.Generator(device="cpu").manual_seed(23)
-    b, n = 2, 5000 + 13
-    grid = torch.relu(torch.randn((b, 2 * c) + hw_g, generator=gen)).to(DEV)[:, c:]          # a channel slice (strided)
-    gcoord = _model_like_coords(gen, b, n, hw_g[0] / sg[0], hw_g[1] / sg[1]).to(DEV)
-    scoord = _model_like_coords(gen, b, n, hw_o[0] / ss[0], hw_o[1] / ss[1]).to(DEV)
-    out = torch.zeros((b,) + hw_o + (c,), device=DEV)
-    rows = torch.zeros((b, n, c + 8), device=DEV)
-    ops.gather_scatter(grid, gcoord, sg, scoord, ss, out=out, pts_out=rows[:, :, 8:])
-    pts = ops.bilinear_gather(grid, gcoord, sg)
-    want = torch.zeros((b, c) + hw_o, device=DEV)
-    ops.voxel_maxpool_fwd(pts, scoord, want, hw_o, ss)
-    assert torch.equal(rows[:, :, 8:], pts.permute(0, 2, 1))
-    assert torch.equal(out.permute(0, 3, 1, 2), want)
-    nchw = torch.full((b, c + 5) + hw_o, 3.0, device=DEV)
-    ops.nhwc_to_nchw(out, nchw[:, 5:])
-    assert torch.equal(nchw[:, 5:], want) and (nchw[:, :5] == 3.0).all()
-    rows2 = torch.zeros((b, n, c), device=DEV)
-    ops.gather_scatter(grid, gcoord, sg, pts_out=rows2)                                       # gather only
-    assert torch.equal(rows2, pts.permute(0, 2, 1))
-
-
-def test_downsample_epilogue_channels_last_kernel():
-    import torch.nn.functional as F
-    gen = torch.Generator(device="cpu").manual_seed(29)
-    for stride, hw in ((2, (64, 200)), (1, (16, 70))):
-        p = torch.randn((2, 64) + hw, generator=gen).to(DEV)
-        a = torch.randn((2, 64, (hw[0] - 1) // stride + 1, (hw[1] - 1) // stride + 1), generator=gen).to(DEV)
-        bias = torch.randn(64, generator=gen).to(DEV)
-        want = torch.relu(a + bias[None, :, None, None] + F.max_pool2d(p, 3, stride, 1))
-        big = torch.zeros((2, 80) + tuple(a.shape[2:]), device=DEV)
-        ops.downsample_epilogue(a.contiguous(memory_format=torch.channels_last), p.contiguous(memory_format=torch.channels_last),
-                                bias, stride, out=big[:, 16:])
-        assert (big[:, 16:] - want).abs().max().item() < 1e-6 and big[:, :16].abs().max().item() == 0
-
-
 def test_vote_full_size_local_map_bit_exact():
     """A realistic local map (8 history scans + the current one, 120k points each, ~1 M points) through the packed
     vote table against the numpy restatement of the reference's dense histogram + argmax."""

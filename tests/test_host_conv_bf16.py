@@ -95,6 +95,14 @@ def test_unknown_precision_refused():
         engine.InferenceEngine(None, layout="nchw", conv_precision="bf16")
 
 
+def test_removed_nchw_layout_refused_before_the_net_is_touched():
+    """The NCHW engine is gone: any layout but "cl" is refused at default precision too, and before the constructor
+    reads anything from net (None here)."""
+    with pytest.raises(ValueError) as err:
+        engine.InferenceEngine(None, layout="nchw")
+    assert "cl" in str(err.value) and "nchw" in str(err.value)
+
+
 def test_model_attribute_default():
     from streammos_amd.refapi.config import StreamMOS as cfg
     from streammos_amd.refapi.models import StreamMOS
