@@ -1103,6 +1103,10 @@ _TAP_GEMM_OWN = _TAP_GEMM == "conv"
 _TAP_PARTS = int(os.environ.get("SMOS_TAP_PARTS", "3"))      # column ranges per source in the tap-product launch (tuning knob)
 # x pass and y pass in one launch (smos_upconv_xy) where the geometry allows; "0": always the two launches (A/B, same results)
 _UPCONV_XY = os.environ.get("SMOS_UPCONV_XY", "1") != "0"
+# bytes of a tap-product matrix one smos_tfusion_project job may cover (it addresses its operands with 32-bit buffer offsets) and
+# the most rows of one job (the kernel takes fewer than 2^22 tokens); upconv3x3 cuts larger sources into row ranges of 64n rows
+_TAP_JOB_BYTES = (1 << 31) - 4096
+_TAP_JOB_ROWS = (1 << 22) - 64
 
 
 def upconv_tap_products(x, wt):
@@ -1148,7 +1152,7 @@ def upconv3x3(conv_a, bias, sources, act, out=None):
                 z = torch.empty((rows.shape[0], 9 * wt.cout), dtype=torch.float32, device=x.device)
                 pre[i] = z
                 n = 9 * wt.cout // parts
-                limit = ((1 << 31) - 4096) // (9 * wt.cout * 4) // 64 * 64          # rows whose z (and x) slice stays below 2 GiB
+                limit = min(_TAP_JOB_ROWS, _TAP_JOB_BYTES // (9 * wt.cout * 4) // 64 * 64)    # rows whose z (and x) slice stays below 2 GiB
                 for r0 in range(0, rows.shape[0], limit):
                     r1 = min(r0 + limit, rows.shape[0])
                     for k, ws_k in enumerate(wt.stream(parts)):
