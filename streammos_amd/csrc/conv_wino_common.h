@@ -1,4 +1,4 @@
-// Declarations of csrc/conv_wino.hip: argument block,
+// Shared by csrc/conv_wino.hip and csrc/conv_wino1d.hip: conv_wino's argument block,
 // item coordinates, LDS image constants of the staged input region, the 16-lane row sum.
 #pragma once
 #include "conv_common.h"

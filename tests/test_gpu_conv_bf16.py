@@ -299,8 +299,7 @@ def test_engine_matches_emulated_mode(model, monkeypatch):
         assert d.max().item() <= 1e-2 and d.mean().item() <= 5e-4 and agree >= 0.999, (i, d.max().item(), agree)
 
 
-_FP32_KERNELS = ("conv_cl", "conv_rows_cl", "conv_wino_cl", "conv_wino1d_cl", "basic_block_cl", "unbalance_block_cl",
-                 "conv_wino_chain_cl")
+_FP32_KERNELS = ("conv_cl", "conv_rows_cl", "conv_wino_cl", "conv_wino1d_cl", "basic_block_cl", "unbalance_block_cl")
 
 
 def test_routing(model, monkeypatch):
