@@ -340,7 +340,8 @@ int smos_upconv_ypass(const float* conv_a, int64_t a_pitch, const float* bias, c
  * 1x1 K1->M1 + ReLU -> 1x1 M1->M2 + ReLU -> 1x1 M2->M3 + bias, out [B, M3, N]; one kernel, intermediates in registers
  * (csrc/point_head.hip).  Built for 192 -> 96 -> 64 -> M3 <= 32.  wprep: smos_point_head_weight_floats() floats =
  * the three weight matrices in MFMA operand order followed by the biases (b3 padded to 32):
- *   A1[(mt*96 + s)*64 + lane] = W1[mt*32 + (lane&31)][(lane>>5)*96 + s]
+ *   A1[(mt*96 + s)*64 + lane] = W1[mt*32 + (lane&31)][64*(s>>5) + 32*(lane>>5) + (s&31)]   (a row is three 64-channel
+ *       segments; k-steps [32t, 32t+32) walk segment t, lane half h its channels [32h, 32h+32))
  *   A2[(mt*48 + s)*64 + lane] = W2[mt*32 + (lane&31)][ch(s, lane>>5)],  A3[s*64 + lane] = W3[lane&31][ch(s, lane>>5)] (0 beyond M3)
  *   with ch(s, h) = 32 (s >> 4) + 8 ((s & 15) >> 2) + 4 h + (s & 3)   (the accumulator order of the previous layer). */
 int64_t smos_point_head_weight_floats(void);
@@ -352,6 +353,17 @@ int smos_point_head(const float* rows, int64_t row_pitch, const float* wprep, fl
  * [*n_live, N) are written as zeros without being computed.  The streaming runner's form; AttNet.infer computes all N. */
 int smos_point_head_live(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N, int64_t K1,
                          int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, smos_stream_t stream);
+
+/* smos_point_head_live with the middle 64-channel segment of every row gathered from a channels-last map instead of read from
+ * the row: channel 64 + c of point (b, n) = BilinearSample of grid [B, Hg, Wg, *] (pixel pitch grid_pitch floats, channels
+ * [0, 64) read, 16-byte aligned, < 2 GiB) at gcoord * gscale, with the position arithmetic, tap order and absent-tap rule of
+ * smos_gather_scatter_cl_view (gcoord, Kg, g_batch_stride, gscale as there).  Floats [64, 128) of `rows` are neither read nor
+ * written; the logits equal those of smos_gather_scatter_cl_view(pts_out = rows + 64) followed by smos_point_head_live bit
+ * for bit.  Replaces networks/backbone.py:453-475 (bev_grid2point) + :387-413,188-196 of the decoder's tail in one launch. */
+int smos_point_head_gather_live(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N,
+                                int64_t K1, int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, const float* grid,
+                                int64_t grid_pitch, int64_t Hg, int64_t Wg, const float* gcoord, int32_t Kg,
+                                int64_t g_batch_stride, const float* gscale, smos_stream_t stream);
 
 /* smos_pointnet_scatter with a COMPACT target: rows [n_rows, T*cout] (zero-filled by smos_stem_scan) instead of
  * the dense [B,H,W,T*cout] grid; the features of cell (b, y, x) go to row row_of[b][y][x] (smos_stem_scan). */

@@ -44,6 +44,7 @@ SIGNATURES = {
     "smos_point_head_weight_floats": [],
     "smos_point_head": [vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, vp],
     "smos_point_head_live": [vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp],
+    "smos_point_head_gather_live": [vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, vp, i32, i64, c_f32p, vp],
     "smos_conv_cl_sum_chunks": [i64, i64],
     "smos_conv_cl": [vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "smos_conv_rows_cl": [vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp],
@@ -82,6 +83,8 @@ SIGNATURES = {
     "smos_label_count_voted": [vp, i64, vp, vp, vp, i32, vp, vp],
 }
 
+ABI_VERSION = 1      # SMOS_ABI_VERSION of the include/smos.h these signatures were written against
+
 _lib = None
 
 
@@ -102,6 +105,13 @@ def load():
     if os.path.isfile(bundled):
         ctypes.CDLL(bundled, mode=ctypes.RTLD_GLOBAL)
     lib = ctypes.CDLL(LIB_PATH)
+    # a library of another ABI (a stale build, a diagnostic build from another tree) must not be called through these signatures
+    lib.smos_abi_version.argtypes = []
+    lib.smos_abi_version.restype = ctypes.c_int
+    have = lib.smos_abi_version()
+    if have != ABI_VERSION:
+        raise RuntimeError("streammos_amd: %s has ABI version %d, this package binds version %d -- rebuild it "
+                           "(`python -m streammos_amd.build -f`)" % (LIB_PATH, have, ABI_VERSION))
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes

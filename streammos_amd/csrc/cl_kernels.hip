@@ -282,12 +282,6 @@ struct GsClArgs {
   float gsy, gsx, ssy, ssx;
 };
 
-__device__ __forceinline__ float pix_cl(float c, float s, int size) {
-  const float sm1 = (float)(size - 1);
-  const float gn = __fsub_rn(__fdiv_rn(__fmul_rn(__fmul_rn(2.0f, c), s), sm1), 1.0f);
-  return __fmul_rn(__fdiv_rn(__fadd_rn(gn, 1.0f), 2.0f), sm1);
-}
-
 // value of lane j of the caller's group.  kC = 64: the group is the wave and j is wave-uniform, so a scalar lane read
 // (v_readlane, result in an SGPR) replaces the LDS shuffle: 0.082 -> 0.070 ms per launch.  kC = 32 (two groups per wave)
 // keeps the shuffle: two lane reads + a select measured slower (0.067 vs 0.045 ms).
@@ -313,19 +307,7 @@ __global__ __launch_bounds__(kBlock) void gather_scatter_cl(GsClArgs a) {
     int cell = -1;
     if (n < a.N) {
       const float* cr = a.gcoord + (int64_t)b * a.gbs + (int64_t)n * a.Kg;
-      const float iy = pix_cl(cr[0], a.gsy, a.Hg), ix = pix_cl(cr[1], a.gsx, a.Wg);
-      const float fy = floorf(iy), fx = floorf(ix);
-      const float wx1 = ix - fx, wx0 = (fx + 1.0f) - ix, wy1 = iy - fy, wy0 = (fy + 1.0f) - iy;
-      const bool fin = (iy > -2.0f) && (iy < (float)(a.Hg + 1)) && (ix > -2.0f) && (ix < (float)(a.Wg + 1));
-      const int y0 = fin ? (int)fy : -5, x0 = fin ? (int)fx : -5;
-      const float w4[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int y = y0 + (k >> 1), xx = x0 + (k & 1);
-        const bool in = (y >= 0) && (y < a.Hg) && (xx >= 0) && (xx < a.Wg);
-        off[k] = in ? y * a.Wg + xx : -1;
-        wt[k] = in ? w4[k] : 0.0f;
-      }
+      bilinear_taps_cl(cr[0], cr[1], a.gsy, a.gsx, a.Hg, a.Wg, off, wt);   // smos_common.h
       if (a.scoord) {
         const float* sr = a.scoord + (int64_t)b * a.sbs + (int64_t)n * a.Ks;
         const float py = __fmul_rn(sr[0], a.ssy), px = __fmul_rn(sr[1], a.ssx);
@@ -436,19 +418,7 @@ __global__ __launch_bounds__(kBlock) void gather_scatter_cl4(GsClArgs a) {
     int cell = -1;
     if (n < a.N) {
       const float* cr = a.gcoord + (int64_t)b * a.gbs + (int64_t)n * a.Kg;
-      const float iy = pix_cl(cr[0], a.gsy, a.Hg), ix = pix_cl(cr[1], a.gsx, a.Wg);
-      const float fy = floorf(iy), fx = floorf(ix);
-      const float wx1 = ix - fx, wx0 = (fx + 1.0f) - ix, wy1 = iy - fy, wy0 = (fy + 1.0f) - iy;
-      const bool fin = (iy > -2.0f) && (iy < (float)(a.Hg + 1)) && (ix > -2.0f) && (ix < (float)(a.Wg + 1));
-      const int y0 = fin ? (int)fy : -5, x0 = fin ? (int)fx : -5;
-      const float w4[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int y = y0 + (k >> 1), xx = x0 + (k & 1);
-        const bool in = (y >= 0) && (y < a.Hg) && (xx >= 0) && (xx < a.Wg);
-        off[k] = in ? y * a.Wg + xx : -1;
-        wt[k] = in ? w4[k] : 0.0f;
-      }
+      bilinear_taps_cl(cr[0], cr[1], a.gsy, a.gsx, a.Hg, a.Wg, off, wt);   // smos_common.h
       if (kScatter) {
         const float* sr = a.scoord + (int64_t)b * a.sbs + (int64_t)n * a.Ks;
         const float py = __fmul_rn(sr[0], a.ssy), px = __fmul_rn(sr[1], a.ssx);
@@ -495,15 +465,7 @@ __global__ __launch_bounds__(kBlock) void gather_scatter_cl4(GsClArgs a) {
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         const int j = grp * kL + i0 + u;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const bool has = o[u][k] >= 0;
-          v.x = has ? v.x + g[u][k].x * w[u][k] : v.x;
-          v.y = has ? v.y + g[u][k].y * w[u][k] : v.y;
-          v.z = has ? v.z + g[u][k].z * w[u][k] : v.z;
-          v.w = has ? v.w + g[u][k].w * w[u][k] : v.w;
-        }
+        const float4 v = bilinear_sum_cl(g[u], o[u], w[u]);                 // smos_common.h
         if (pb && n0 + j < a.N) *reinterpret_cast<float4*>(pb + (int64_t)j * a.po_n) = v;
         if (kScatter) *reinterpret_cast<float4*>(tile + j * kC + 4 * l) = v;
       }

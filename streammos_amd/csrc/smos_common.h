@@ -65,6 +65,47 @@ __device__ __forceinline__ double pose_row_f64(const double* m, double x, double
   return __dadd_rn(__fma_rn(m[2], z, __fma_rn(m[1], y, __dmul_rn(m[0], x))), m[3]);
 }
 
+// BilinearSample (networks/backbone.py:453-475) on a channels-last map, position side: grid_sample's float32 normalise /
+// un-normalise round trip, then the four taps (k = 2 dy + dx) as pixel offsets y * Wg + x (-1: the tap lies outside the map, zeros
+// padding) and weights.  One definition for gather_scatter_cl / _cl4 (csrc/cl_kernels.hip) and for the point head that gathers
+// its own BEV rows (csrc/point_head.hip): the same bits everywhere.
+__device__ __forceinline__ float pix_cl(float c, float s, int size) {
+  const float sm1 = (float)(size - 1);
+  const float gn = __fsub_rn(__fdiv_rn(__fmul_rn(__fmul_rn(2.0f, c), s), sm1), 1.0f);
+  return __fmul_rn(__fdiv_rn(__fadd_rn(gn, 1.0f), 2.0f), sm1);
+}
+
+__device__ __forceinline__ void bilinear_taps_cl(float cy, float cx, float gsy, float gsx, int Hg, int Wg, int (&off)[4], float (&wt)[4]) {
+  const float iy = pix_cl(cy, gsy, Hg), ix = pix_cl(cx, gsx, Wg);
+  const float fy = floorf(iy), fx = floorf(ix);
+  const float wx1 = ix - fx, wx0 = (fx + 1.0f) - ix, wy1 = iy - fy, wy0 = (fy + 1.0f) - iy;
+  const bool fin = (iy > -2.0f) && (iy < (float)(Hg + 1)) && (ix > -2.0f) && (ix < (float)(Wg + 1));
+  const int y0 = fin ? (int)fy : -5, x0 = fin ? (int)fx : -5;
+  const float w4[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int y = y0 + (k >> 1), xx = x0 + (k & 1);
+    const bool in = (y >= 0) && (y < Hg) && (xx >= 0) && (xx < Wg);
+    off[k] = in ? y * Wg + xx : -1;
+    wt[k] = in ? w4[k] : 0.0f;
+  }
+}
+
+// The value side for four channels: the sum over the taps that exist, in tap order (an absent tap is skipped by a select on the
+// value, whatever its load returned).
+__device__ __forceinline__ float4 bilinear_sum_cl(const float4 (&g)[4], const int (&off)[4], const float (&wt)[4]) {
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const bool has = off[k] >= 0;
+    v.x = has ? v.x + g[k].x * wt[k] : v.x;
+    v.y = has ? v.y + g[k].y * wt[k] : v.y;
+    v.z = has ? v.z + g[k].z * wt[k] : v.z;
+    v.w = has ? v.w + g[k].w * wt[k] : v.w;
+  }
+  return v;
+}
+
 struct Scale4 {
   float v[4];
 };

@@ -162,6 +162,8 @@ class InferenceEngine:
                            (rp.weight.detach().contiguous(), rp.bias.detach().contiguous()))
         # fused point head (csrc/point_head.hip) when the head has the reference's 192 -> 96 -> 64 -> 3 shape
         self.fused_head = os.environ.get("SMOS_FUSED_HEAD", "1") != "0"
+        # the fused head gathers the decoder's BEV rows itself instead of reading them back from a gather launch (A/B switch)
+        self.head_gather = os.environ.get("SMOS_HEAD_GATHER", "1") != "0"
         self.head_w = self.refine_w = None
         try:
             self.head_w = ops.point_head_prepare(self.post1, self.post2, self.pred)
@@ -238,16 +240,26 @@ class InferenceEngine:
         except (RuntimeError, AttributeError):
             return torch.relu_(torch.addmm(wb[1], x, w.t()))
 
-    def _point_heads(self, fuse, aux, k, x2, n_live=None):
+    def _head_gathers(self, fuse, bev_feat, o1, o2):
+        """True where the fused head may gather the BEV third of the point rows itself: it is the only reader of that third
+        (stage-1 model: no refine head; the aux heads read maps, not rows) and the kernel's layout holds."""
+        return (self.head_gather and self.fused_head and self.head_w is not None and self.refine is None
+                and (o1, o2) == (64, 128) and fuse.shape[2] == 192 and fuse.stride(1) % 4 == 0
+                and bev_feat.data_ptr() % 16 == 0 and bev_feat.stride(3) % 4 == 0)
+
+    def _point_heads(self, fuse, aux, k, x2, n_live=None, gather=None):
         """CatFusion + PredBranch as point-major GEMMs: [B*N, 192] -> 96 -> 64 -> 3 (and the stage-2 refine head).
-        n_live (device int32, runner only): real points at the front of every sample; the padding tail's logits are zeros."""
+        n_live (device int32, runner only): real points at the front of every sample; the padding tail's logits are zeros.
+        gather (see ops.point_head; only where _head_gathers() holds): the BEV third of `fuse` has not been written."""
         bs, n = fuse.shape[0], fuse.shape[1]
         rows = fuse.view(bs * n, -1)
         a3 = tuple(aux) if isinstance(aux, (tuple, list)) else (aux[:, :k], aux[:, k:2 * k], aux[:, 2 * k:])
 
         def head(l1, l2, pr, fused):
             if self.fused_head and fused is not None and fuse.stride(1) % 4 == 0:
-                return ops.point_head(fuse, fused[0], fused[1], n_live=n_live).unsqueeze(-1)
+                return ops.point_head(fuse, fused[0], fused[1], n_live=n_live, gather=gather).unsqueeze(-1)
+            if gather is not None:
+                raise RuntimeError("InferenceEngine: the BEV rows were left to the fused point head, which does not run")
             z = self._linear_relu(self._linear_relu(rows, l1), l2)
             out = torch.addmm(pr[1], z, pr[0].view(pr[0].shape[0], -1).t())
             return out.view(bs, n, -1).permute(0, 2, 1).contiguous().unsqueeze(-1)
@@ -582,5 +594,7 @@ class InferenceEngine:
             y = self._conv(dec_in, self.conv_1[0], self.conv_1[1], LEAKY)
             aux = F.conv2d(dec_in, self.aux[0], self.aux[1]) if want_aux else (None, None, None)
         bev_feat = self._conv(y, self.conv_2[0], self.conv_2[1], LEAKY)
+        if self._head_gathers(fuse, bev_feat, o1, o2):
+            return self._point_heads(fuse, aux, k, x2, n_live, gather=(bev_feat, bev_xy, self.grid2point_scale))
         ops.gather_scatter_cl(bev_feat, bev_xy, self.grid2point_scale, pts_out=fuse[:, :, o1:o2], n_live=n_live)
         return self._point_heads(fuse, aux, k, x2, n_live)

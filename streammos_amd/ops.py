@@ -434,6 +434,15 @@ def pointnet_scatter(xyzi, coord, w1, b1, w2, b2, bev, pts_out=None, zero_fill=F
     return bev
 
 
+def point_head_k_order():
+    """[96, 2] int64: the input channel k-step s of layer 1 feeds to lane half h.  A row is three 64-channel segments (point
+    MLP | BEV | range view); steps [32 t, 32 t + 32) walk segment t, lane half h its channels [32 h, 32 h + 32) -- the same walk
+    for both halves, so that one segment (the BEV one, smos_point_head_gather_live) can come from somewhere else than the row."""
+    s = torch.arange(96)[:, None]
+    h = torch.arange(2)[None, :]
+    return 64 * (s >> 5) + 32 * h + (s & 31)
+
+
 def point_head_prepare(l1, l2, l3):
     """(W1 [96,192(,1,1)], b1), (W2 [64,96], b2), (W3 [M3,64], b3) -> the flat weight block smos_point_head expects."""
     w1, b1 = l1[0].reshape(l1[0].shape[0], -1).float(), l1[1].float()
@@ -444,7 +453,7 @@ def point_head_prepare(l1, l2, l3):
     dev = w1.device
     lane = torch.arange(64, device=dev)
     m, h = lane & 31, lane >> 5
-    a1 = w1.view(3, 32, 2, 96).permute(0, 3, 2, 1).reshape(3, 96, 64)                     # (mt, s, h*32 + m)
+    a1 = w1.view(3, 32, 192)[:, :, point_head_k_order().to(dev)].permute(0, 2, 3, 1).reshape(3, 96, 64)   # (mt, s, h*32 + m)
 
     def acc_order(n_steps):                                                               # ch(s, h) for s < n_steps
         s = torch.arange(n_steps, device=dev)[:, None]
@@ -462,24 +471,40 @@ def point_head_prepare(l1, l2, l3):
     return flat, int(w3.shape[0])
 
 
-def point_head(rows, wprep, m3, out=None, n_live=None):
+def point_head(rows, wprep, m3, out=None, n_live=None, gather=None):
     """rows [B, N, >=192] float32 (row stride a multiple of 4 floats) -> logits [B, m3, N].
     n_live: optional device int32 tensor (its first element is read): the number of REAL points at the front of every sample;
     the logits of the scan's padding tail [n_live, N) come back as zeros without being computed (the streaming runner's form:
-    val_StreamMOS.py:113 cuts them off)."""
+    val_StreamMOS.py:113 cuts them off).
+    gather = (grid, gcoord, gscale): channels [64, 128) of every row are not read from `rows` but gathered by the kernel itself
+    from the channels-last [B, 64, Hg, Wg] view `grid` at gcoord * gscale -- gather_scatter_cl(grid, gcoord, gscale,
+    pts_out=rows[:, :, 64:128]) followed by point_head(rows, ...), bit for bit, in one launch and without that pass over the rows."""
     _require_cuda("point_head", rows, wprep, out, n_live)
     if rows.dtype != torch.float32 or rows.dim() != 3 or rows.stride(2) != 1 or rows.stride(0) != rows.shape[1] * rows.stride(1):
         raise RuntimeError("point_head: rows must be a float32 [B, N, C] tensor with dense point rows")
     if n_live is not None and (n_live.dtype != torch.int32 or n_live.numel() < 1):
         raise RuntimeError("point_head: n_live must be a device int32 tensor")
     b, n = rows.shape[0], rows.shape[1]
+    if gather is not None:
+        grid, gcoord, gscale = gather
+        _require_cuda("point_head", grid, gcoord)
+        if grid.dtype != torch.float32 or grid.shape[0] != b or grid.shape[1] != 64:
+            raise RuntimeError("point_head: the gathered map must be a float32 channels-last [B, 64, Hg, Wg] view, got %s" % (tuple(grid.shape),))
+        gp = _cl("point_head", grid)
+        kg, gbs = _coord_view("point_head", gcoord, b, n)
     if out is None:
         out = torch.empty((b, m3, n), dtype=torch.float32, device=rows.device)
     lib = _lib.load()
+    live = n_live.data_ptr() if n_live is not None else None
     with _on(rows.device), profiling.span_f("point_head[%dx%d]", (b, n)):
-        rc = lib.smos_point_head_live(rows.data_ptr(), rows.stride(1), wprep.data_ptr(), out.data_ptr(), b, n, 192, 96, 64, m3,
-                                      n_live.data_ptr() if n_live is not None else None, _stream(rows))
-    _lib.check(rc, "smos_point_head_live")
+        if gather is None:
+            rc = lib.smos_point_head_live(rows.data_ptr(), rows.stride(1), wprep.data_ptr(), out.data_ptr(), b, n, 192, 96, 64, m3,
+                                          live, _stream(rows))
+        else:
+            rc = lib.smos_point_head_gather_live(rows.data_ptr(), rows.stride(1), wprep.data_ptr(), out.data_ptr(), b, n, 192, 96, 64,
+                                                 m3, live, grid.data_ptr(), gp, grid.shape[2], grid.shape[3], gcoord.data_ptr(), kg,
+                                                 gbs, _lib.f32_array(gscale), _stream(rows))
+    _lib.check(rc, "smos_point_head_live" if gather is None else "smos_point_head_gather_live")
     return out
 
 
