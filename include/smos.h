@@ -324,13 +324,21 @@ int smos_conv_wino1d_cl(const float* x, int64_t x_pitch, const float* wprep, con
  *                      conv_a [B, Ho, Wo, *] (row pitch a_pitch) is the direct convolution of the channels that are not
  *                      upsampled; t2 may be NULL; act 0 none, 1 ReLU, 2 LeakyReLU(0.01); interpolation with ATen's
  *                      align_corners=True weights.
- *   smos_upconv_xy     the two passes in one launch, t kept in registers (same operations in the same order: same
+ *   smos_upconv_xy     the two passes in one launch, t kept on the CU (same operations in the same order: same
  *                      results): out <- act(conv_a + bias + sum over z1 [B, H1, W1, 9*C], z2 [B, H2, W2, 9*C] (one may
- *                      be NULL)).  Only for sources of at most half the output height: smos_upconv_xy_ok(Hs, Ho) != 0. */
+ *                      be NULL)).  Only for sources of at most half the output height: smos_upconv_xy_ok(Hs, Ho) != 0.
+ *                      Refused as well (the kernel addresses a row with 32-bit byte offsets): a_pitch or out_pitch below C,
+ *                      a row of conv_a, out (Wo * pitch) or z (Ws * 9 * C) of 2^29 floats = 2 GiB or more. */
 int smos_upconv_xy_ok(int64_t Hs, int64_t Ho);
 int smos_upconv_xy(const float* conv_a, int64_t a_pitch, const float* bias, const float* z1, int64_t H1, int64_t W1, const float* z2,
                    int64_t H2, int64_t W2, float* out, int64_t out_pitch, int64_t B, int64_t Ho, int64_t Wo, int64_t C, int32_t act,
                    smos_stream_t stream);
+/*   smos_upconv_xy_units  smos_upconv_xy with the unit geometry given: `strip` output rows per unit of work (8, 16 or 32;
+ *                      smos_upconv_xy chooses it from the sizes) and at most `max_blocks` blocks (0: no cap; fewer blocks
+ *                      than units make a block walk several units).  Same results for every choice. */
+int smos_upconv_xy_units(const float* conv_a, int64_t a_pitch, const float* bias, const float* z1, int64_t H1, int64_t W1,
+                         const float* z2, int64_t H2, int64_t W2, float* out, int64_t out_pitch, int64_t B, int64_t Ho, int64_t Wo,
+                         int64_t C, int32_t act, int32_t strip, int64_t max_blocks, smos_stream_t stream);
 int smos_upconv_xpass(const float* z, float* t, int64_t B, int64_t Hs, int64_t Ws, int64_t C, int64_t Wo, smos_stream_t stream);
 int smos_upconv_ypass(const float* conv_a, int64_t a_pitch, const float* bias, const float* t1, int64_t H1, const float* t2,
                       int64_t H2, float* out, int64_t out_pitch, int64_t B, int64_t Ho, int64_t Wo, int64_t C, int32_t act,

@@ -67,6 +67,7 @@ SIGNATURES = {
     "smos_upconv_ypass": [vp, i64, vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, i32, vp],
     "smos_upconv_xy_ok": [i64, i64],
     "smos_upconv_xy": [vp, i64, vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i64, i64, i32, vp],
+    "smos_upconv_xy_units": [vp, i64, vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i64, i64, i32, i32, i64, vp],
     "smos_prep_transform_mask": [vp, i64, c_f64p, c_f64p, vp, vp, vp],
     "smos_prep_emit": [vp, vp, vp, i64, i32, i32, i64, i32, c_f32p, c_f32p, c_f64p, c_i64p, c_f64p, vp, vp, vp, vp],
     "smos_prep_unpad_labels": [vp, i64, vp, vp, i64, vp, vp],

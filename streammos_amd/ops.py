@@ -1170,6 +1170,26 @@ def upconv3x3(conv_a, bias, sources, act, out=None):
     return out
 
 
+def upconv_xy_units(conv_a, bias, z1, z2, act, strip, max_blocks=0, out=None):
+    """smos_upconv_xy_units: the one-launch interpolation of upconv3x3 from given tap products, with the unit geometry
+    given -- `strip` output rows per unit of work (8, 16 or 32) and at most `max_blocks` blocks (0: no cap).  z1, z2: (z
+    [B*Hs*Ws, 9*C] contiguous, Hs, Ws) or None (at least one).  conv_a, out: channels-last [B,C,Ho,Wo] views (out=None:
+    in place).  Same results for every strip and cap (tests, tools/ubench_upconv.py)."""
+    _require_cuda("upconv_xy_units", conv_a, bias, out, z1 and z1[0], z2 and z2[0])
+    b, c, ho, wo = conv_a.shape
+    if out is None:
+        out = conv_a
+    for z in (z1, z2):
+        if z is not None and (tuple(z[0].shape) != (b * z[1] * z[2], 9 * c) or not z[0].is_contiguous()):
+            raise RuntimeError("upconv_xy_units: tap products must be a contiguous [B*Hs*Ws, 9*C] matrix, got %s" % (tuple(z[0].shape),))
+    (p1, h1, w1), (p2, h2, w2) = ((z[0].data_ptr(), z[1], z[2]) if z is not None else (None, 0, 0) for z in (z1, z2))
+    with _on(conv_a.device):
+        _lib.check(_lib.load().smos_upconv_xy_units(conv_a.data_ptr(), _cl("upconv_xy_units", conv_a), bias.data_ptr(), p1, h1, w1, p2, h2, w2,
+                                                    out.data_ptr(), _cl("upconv_xy_units", out), b, ho, wo, c, int(act), int(strip),
+                                                    int(max_blocks), _stream(conv_a)), "smos_upconv_xy_units")
+    return out
+
+
 STEM_TAPS = (1, 2, 2, 4)      # 3x3 taps that reach an output pixel under stride 2, per parity class (y&1)*2 + (x&1)
 
 
