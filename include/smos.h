@@ -240,6 +240,20 @@ int smos_tfusion_layer(const float* sampled, const float* query, int64_t q_pitch
                        float* out, int64_t o_pitch, float* qp_next, int64_t nq, int64_t tokens, int64_t ffn, float eps1,
                        float eps2, smos_stream_t stream);
 
+/* The decoder's tap products on the bf16 matrix pipe at fp32 accuracy (csrc/tap_bf16x3.hip): out[j] = x[j] W[j]^T for up to
+ * eight jobs in one launch, every fp32 operand split exactly into three bf16 limbs (hi = bf16(v), mid = bf16(v - hi), lo =
+ * bf16(v - hi - mid), round-to-nearest-even) and the six leading limb products summed in fp32 in a fixed order.  The job
+ * contract of smos_tfusion_project without a bias: x[j] [tokens[j], *] rows of 128 channels, pitch x_pitch[j] floats;
+ * wlimbs[j] = streammos_amd.ops.tap_limbs_pack(W[j]): the limbs of W as bf16 MFMA fragments in the kernel's stream order
+ * [tile of 32 outputs][k step 0..7][lo, mid, hi][lane 0..63][8] -- lane (r = lane & 31, h = lane >> 5), element j holds
+ * W_limb[32 tile + r][16 step + 8 h + j], cout rounded up to a multiple of 32 with zero rows; out[j] [tokens[j], *] rows of pitch out_pitch[j] >= cout[j] (a job may fill a column range of a wider matrix);
+ * cout a multiple of 4, <= 2048; 0 < tokens < 2^22; operands below 2 GiB.  Inputs: finite, and large enough for the low limb
+ * to stay a normal number (|v| >~ 2^-110, or 0); a non-finite input gives a non-finite output (NaN where fp32 gives Inf).
+ * Deterministic; a column range of W gives the bits of the whole matrix. */
+int smos_tap_products_bf16x3(int32_t n_jobs, const float* const* x, const int64_t* x_pitch, const void* const* wlimbs,
+                             float* const* out, const int64_t* out_pitch, const int64_t* cout, const int64_t* tokens,
+                             smos_stream_t stream);
+
 /* out = LayerNorm(x + res) over rows of C floats (res may be NULL): the residual + norm steps of a DeformAttnLayer
  * (multi_view_encoder.py:314-320).  C in {64, 128, 256, 512}; biased variance, eps inside the square root (torch). */
 int smos_add_layer_norm(const float* x, const float* res, const float* gamma, const float* beta, float* out, int64_t rows,

@@ -14,7 +14,7 @@ KIND = (
     (("msda_fwd",), "msda_fwd[", 1),
     (("pool_branch",), "downsample_pool_branch[", 1),
     (("tfusion_layer",), "tfusion_layer[", 1),
-    (("tfusion_project",), "tfusion_project[", 1),
+    (("tfusion_project", "tap_bf16x3"), "tfusion_project[", 1),      # the tap products keep that label on either kernel (ops.tap_products_bf16x3)
     (("stem_mark", "stem_scan"), "stem_mark+scan[", 2),
 )
 

@@ -62,6 +62,7 @@ SIGNATURES = {
     "smos_tfusion_layer_param_floats": [i64],
     "smos_tfusion_layer_stream_floats": [i64, i32],
     "smos_tfusion_layer": [vp, vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, ctypes.c_float, ctypes.c_float, vp],
+    "smos_tap_products_bf16x3": [i32, ctypes.POINTER(vp), c_i64p, ctypes.POINTER(vp), ctypes.POINTER(vp), c_i64p, c_i64p, c_i64p, vp],
     "smos_conv_wino1d_cl": [vp, i64, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i64, i32, i32, vp],
     "smos_upconv_xpass": [vp, vp, i64, i64, i64, i64, i64, vp],
     "smos_upconv_ypass": [vp, i64, vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, i32, vp],

@@ -1037,6 +1037,78 @@ def tfusion_layer(sampled, query, prep, out=None):
     return out, nxt
 
 
+def tap_limbs_split(w):
+    """float32 w -> (lo, mid, hi) bfloat16 with hi + mid + lo == w exactly: hi = bf16(w), mid = bf16(w - hi), lo = bf16(w - hi -
+    mid), round-to-nearest-even; both subtractions are exact in float32 (csrc/tap_bf16x3.hip splits the activations the same way)."""
+    w = w.float()
+    hi = w.to(torch.bfloat16)
+    r = w - hi.float()
+    mid = r.to(torch.bfloat16)
+    lo = (r - mid.float()).to(torch.bfloat16)
+    return lo, mid, hi
+
+
+def tap_limbs_pack(w):
+    """w [cout, 128] -> the bfloat16 weight stream of one smos_tap_products_bf16x3 job (include/smos.h): cout zero-padded to a
+    multiple of 32, [tile of 32 outputs][k step 0..7][lo, mid, hi][lane = 32 h + r][8] with lane (r, h), element j =
+    limb[32 tile + r][16 step + 8 h + j]: the B fragments of v_mfma_f32_32x32x16_bf16 in the order the kernel consumes them.
+    Works on CPU and GPU tensors."""
+    cout, k = w.shape
+    if k != 128 or cout > 2048:
+        raise RuntimeError("tap_limbs_pack: expected [<=2048, 128], got %s" % (tuple(w.shape),))
+    pad = (cout + 31) // 32 * 32
+    wp = torch.zeros((pad, k), dtype=torch.float32, device=w.device)
+    wp[:cout] = w
+    v = torch.stack(tap_limbs_split(wp)).reshape(3, pad // 32, 32, 8, 2, 8)         # [limb, tile, r, step, h, j]
+    return v.permute(1, 3, 0, 4, 2, 5).reshape(-1).contiguous()                     # [tile, step, limb, h, r, j]
+
+
+def tap_limbs_unpack(stream, cout):
+    """The inverse of tap_limbs_pack: (lo, mid, hi) float32 [cout, 128] of a packed stream."""
+    pad = (cout + 31) // 32 * 32
+    v = stream.reshape(pad // 32, 8, 3, 2, 32, 8).permute(2, 0, 4, 1, 3, 5)         # [limb, tile, r, step, h, j]
+    return tuple(v.reshape(3, pad, 128)[:, :cout].float())
+
+
+def tap_products_bf16x3(jobs):
+    """jobs: up to eight (x [..., 128] float32 token rows, wlimbs = tap_limbs_pack(W), cout[, out: a [tokens, cout] view with
+    contiguous channels, e.g. a column range of a wider matrix]) -> list of [tokens, cout] outputs x W^T, ONE launch
+    (csrc/tap_bf16x3.hip): float32 in and out at float32 accuracy, computed as six bf16 limb products per term on the bf16 matrix
+    pipe.  The job tuple of tfusion_project without a bias; the jobs may have different token counts."""
+    n = len(jobs)
+    if not 1 <= n <= 8:
+        raise RuntimeError("tap_products_bf16x3: 1..8 jobs")
+    xs, pit, ws, outs, ops_, couts, toks = ((ctypes.c_void_p * n)(), (ctypes.c_int64 * n)(), (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)(),
+                                            (ctypes.c_int64 * n)(), (ctypes.c_int64 * n)(), (ctypes.c_int64 * n)())
+    res = []
+    for j, job in enumerate(jobs):
+        x, w, cout = job[0], job[1], int(job[2])
+        _require_cuda("tap_products_bf16x3", x, w)
+        tk, pitch = _token_rows("tap_products_bf16x3", x)
+        if x.shape[-1] != 128:
+            raise RuntimeError("tap_products_bf16x3: 128-channel token rows expected")
+        if w.dtype != torch.bfloat16 or w.numel() != (cout + 31) // 32 * 32 * 128 * 3 or not w.is_contiguous():
+            raise RuntimeError("tap_products_bf16x3: limb stream of %d %s elements for %d outputs" % (w.numel(), w.dtype, cout))
+        if len(job) > 3 and job[3] is not None:
+            out = job[3]
+            _require_cuda("tap_products_bf16x3", out)
+            if out.dim() != 2 or tuple(out.shape) != (tk, cout) or out.stride(1) != 1 or out.dtype != torch.float32:
+                raise RuntimeError("tap_products_bf16x3: out must be a float32 [tokens, cout] view with contiguous channels")
+        else:
+            out = torch.empty((tk, cout), dtype=torch.float32, device=x.device)
+        res.append(out)
+        xs[j], pit[j], ws[j], outs[j], ops_[j], couts[j], toks[j] = x.data_ptr(), pitch, w.data_ptr(), out.data_ptr(), out.stride(0), cout, tk
+    lib = _lib.load()
+    x0 = jobs[0][0]
+    # the label of the fp32 form: bench.py's byte / FLOP model and profiles/label_durations.py price the launch as before
+    label = ("tfusion_project[%s]" % ",".join("%dx128->%d" % (int(toks[j]), int(couts[j])) for j in range(n))
+             if profiling.enabled() else None)
+    with _on(x0.device), profiling.span(label):
+        rc = lib.smos_tap_products_bf16x3(n, xs, pit, ws, outs, ops_, couts, toks, _stream(x0))
+    _lib.check(rc, "smos_tap_products_bf16x3")
+    return res
+
+
 class TapWeights:
     """The per-tap matrices of a 3x3 convolution's input channels [c0, c1) in the forms upconv3x3 uses.  Everything
     derived from the weights lives in this object (owned by the engine that folded them) -- never in a cache keyed by
@@ -1050,6 +1122,7 @@ class TapWeights:
         self.zero = torch.zeros(9 * cout, dtype=torch.float32, device=w.device)
         self._conv = None
         self._stream = None
+        self._limbs = None
 
     def stream(self, parts=1):
         """the tap matrices in the operand order of smos_tfusion_project (Cin = 128), cut into `parts` equal output ranges"""
@@ -1059,6 +1132,15 @@ class TapWeights:
             n = self.nk.shape[0] // parts
             self._stream[parts] = [tfusion_pack_linear(self.nk[i * n:(i + 1) * n]) for i in range(parts)]
         return self._stream[parts]
+
+    def limb_stream(self, parts=1):
+        """the same column ranges as bf16 limb streams, the operand of smos_tap_products_bf16x3 (Cin = 128)"""
+        if self._limbs is None:
+            self._limbs = {}
+        if parts not in self._limbs:
+            n = self.nk.shape[0] // parts
+            self._limbs[parts] = [tap_limbs_pack(self.nk[i * n:(i + 1) * n]) for i in range(parts)]
+        return self._limbs[parts]
 
     def conv_operand(self):
         if self._conv is None:
@@ -1074,8 +1156,9 @@ def upconv_tap_weights(w, c0, c1):
 # The nine tap products: library GEMM by default; "conv" runs them on the own kernel as one 1x1 convolution with 9*C outputs
 # (measured in the step: 236.6 vs 238.8 scans/s -- K = 128 is only four stages per tile, so the epilogue dominates).
 # "tf" (default since round 4): the token-wise Linear kernel of the temporal fusion (csrc/tfusion.hip), both sources in one launch:
-# 0.26 -> 0.2x ms per step against the library GEMMs ("mm")
-_TAP_GEMM = os.environ.get("SMOS_TAP_GEMM", "tf")
+# 0.26 -> 0.2x ms per step against the library GEMMs ("mm").  "x3" (default): the same jobs on the bf16 matrix pipe as three
+# exact bf16 limbs per fp32 operand (csrc/tap_bf16x3.hip), fp32 accuracy kept (profiles/tap_bf16x3.txt)
+_TAP_GEMM = os.environ.get("SMOS_TAP_GEMM", "x3")
 _TAP_GEMM_OWN = _TAP_GEMM == "conv"
 _TAP_PARTS = int(os.environ.get("SMOS_TAP_PARTS", "3"))      # column ranges per source in the tap-product launch (tuning knob)
 # x pass and y pass in one launch (smos_upconv_xy) where the geometry allows; "0": always the two launches (A/B, same results)
@@ -1113,7 +1196,7 @@ def upconv3x3(conv_a, bias, sources, act, out=None):
     fused = _UPCONV_XY and all(lib.smos_upconv_xy_ok(src[0].shape[2], ho) for src in sources)
     zs, ts = [], []
     pre = {}
-    if _TAP_GEMM == "tf":
+    if _TAP_GEMM in ("tf", "x3"):
         # the tap products of every source that has none yet, as jobs of the token-wise Linear kernel: one launch for the usual
         # sizes; a product matrix of 2 GiB and more (8 and more concurrent streams) is cut into row ranges below 2 GiB (a job
         # addresses its operands with 32-bit buffer offsets) and takes as many launches of up to 8 jobs as that needs
@@ -1121,7 +1204,8 @@ def upconv3x3(conv_a, bias, sources, act, out=None):
         if todo:
             # every source's outputs in `parts` column ranges = parts x len(todo) jobs of 64-token blocks:
             # column ranges shorten the last, partly empty round of resident blocks (tools/ubench_taps.py: 0.230 / 0.213 / 0.211 ms for 1 / 2 / 3 ranges; library GEMMs 0.278)
-            parts = _TAP_PARTS if len(todo) * _TAP_PARTS <= 8 and (9 * sources[todo[0]][1].cout) % (64 * _TAP_PARTS) == 0 else 1
+            x3 = _TAP_GEMM == "x3"        # the bf16 limb kernel walks 32-output tiles, the fp32 one slots of 64
+            parts = _TAP_PARTS if len(todo) * _TAP_PARTS <= 8 and (9 * sources[todo[0]][1].cout) % ((32 if x3 else 64) * _TAP_PARTS) == 0 else 1
             jobs = []
             for i in todo:
                 x, wt = sources[i][0], sources[i][1]
@@ -1132,10 +1216,10 @@ def upconv3x3(conv_a, bias, sources, act, out=None):
                 limit = min(_TAP_JOB_ROWS, _TAP_JOB_BYTES // (9 * wt.cout * 4) // 64 * 64)    # rows whose z (and x) slice stays below 2 GiB
                 for r0 in range(0, rows.shape[0], limit):
                     r1 = min(r0 + limit, rows.shape[0])
-                    for k, ws_k in enumerate(wt.stream(parts)):
+                    for k, ws_k in enumerate(wt.limb_stream(parts) if x3 else wt.stream(parts)):
                         jobs.append((rows[r0:r1], ws_k, n, z[r0:r1, k * n:(k + 1) * n]))
             for j0 in range(0, len(jobs), 8):
-                tfusion_project(jobs[j0:j0 + 8])
+                (tap_products_bf16x3 if x3 else tfusion_project)(jobs[j0:j0 + 8])
     with _on(conv_a.device):
         for i_src, src in enumerate(sources):
             x, wt = src[0], src[1]

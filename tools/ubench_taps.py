@@ -1,5 +1,6 @@
-"""Dev: the decoder's tap products ([65536 + 16384 tokens, 128] x [128, 1152]) on tfusion_project with 1 / 2 / 3 column ranges per
-source, against the library GEMM pair."""
+"""Dev: the decoder's tap products ([65536 + 16384 tokens, 128] x [128, 1152]) on tfusion_project (fp32 MFMA) and on
+tap_products_bf16x3 (three bf16 limbs, csrc/tap_bf16x3.hip) with 1 / 2 / 3 / 6 column ranges per source, against the library GEMM
+pair: same buffers, same event bracket, ROUNDS rounds in one process."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -20,14 +21,18 @@ za, zb = torch.empty(65536, 1152, device=dev), torch.empty(16384, 1152, device=d
 t = timeit(lambda: (torch.addmm(wt.zero, xa, wt.kn), torch.addmm(wt.zero, xb, wt.kn)))
 print("library GEMMs: %.4f ms" % t)
 fl = 2.0 * (65536 + 16384) * 128 * 1152
-for parts in (1, 2, 3, 6):
-    n = 1152 // parts
-    jobs = []
-    for x, z in ((xa, za), (xb, zb)):
-        for k, ws in enumerate(wt.stream(parts)):
-            jobs.append((x, ws, n, z[:, k * n:(k + 1) * n]))
-    if len(jobs) > 8:
-        t = timeit(lambda: (ops.tfusion_project(jobs[:parts]), ops.tfusion_project(jobs[parts:])))
-    else:
-        t = timeit(lambda: ops.tfusion_project(jobs))
-    print("tfusion_project, %d column ranges per source: %.4f ms  %.1f TFLOP/s" % (parts, t, fl / t / 1e9), flush=True)
+ROUNDS = int(os.environ.get("ROUNDS", "3"))
+FORMS = (("tfusion_project", ops.tfusion_project, wt.stream), ("tap_products_bf16x3", ops.tap_products_bf16x3, wt.limb_stream))
+for rnd in range(ROUNDS):
+    for parts in (1, 2, 3, 6):
+        n = 1152 // parts
+        for name, op, stream in FORMS:
+            jobs = []
+            for x, z in ((xa, za), (xb, zb)):
+                for k, ws in enumerate(stream(parts)):
+                    jobs.append((x, ws, n, z[:, k * n:(k + 1) * n]))
+            if len(jobs) > 8:
+                t = timeit(lambda: (op(jobs[:parts]), op(jobs[parts:])))
+            else:
+                t = timeit(lambda: op(jobs))
+            print("round %d  %-20s %d column ranges per source: %.4f ms  %.1f TFLOP/s (fp32-equivalent)" % (rnd, name, parts, t, fl / t / 1e9), flush=True)
