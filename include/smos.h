@@ -168,6 +168,39 @@ int smos_dbscan(const float* pts, int64_t n, int64_t pt_stride, double eps, int3
 int smos_box_vote(const float* pts, int64_t n, int64_t pt_stride, const uint8_t* labels, const double* pose_diff,
                   const float* boxes, int32_t K, uint32_t* counts, smos_stream_t stream);
 
+/* The same instance vote with nothing read back: a fixed sequence of launches whose grids depend on n alone.  The
+ * foreground count and the cluster count K exist only in device memory.  None of these calls synchronises.
+ *
+ * smos_instance_cluster: DBSCAN(eps, min_samples) of the points of the WHOLE scan pts[n] whose bf[i] (device, uint8[n])
+ *   is 2, then InstanceVoter.cluster_boxes on the device.  A point with bf != 2 is nobody's neighbour.
+ *   names[i] (device, int32[n]): scan index of the lowest core point of point i's cluster; -1 for noise and for every
+ *     non-foreground point (smos_dbscan's names of the compacted foreground, mapped back to scan indices).
+ *   Clusters of more than min_points points are kept: boxes[slot] (device, float32[max_boxes][6]) = (lo_x, lo_y, z0,
+ *     hi_x, hi_y, z1) with lifted = lo_z + floor_lift in float32, z0 / z1 = min / max(lifted, hi_z); a box with hi_z == lo_z
+ *     or any hi == lo gets lo = +inf (it contains nothing).  slot_of[name] (device, int32[n]) = the cluster's slot, -1
+ *     for every other index.  *k_dev (device int32) = number of slots used; slot order is unspecified.  If more than
+ *     max_boxes (1..2048) clusters are kept, bit 0 of *status (device int32, written by every call) is set, *k_dev =
+ *     max_boxes and the clusters beyond keep slot -1.
+ *   work: smos_instance_work_bytes(n) bytes of device scratch, 256-byte aligned; a larger one does as well, and nothing
+ *     in it has to survive between calls.  n == 0: *k_dev = *status = 0, nothing else is touched.
+ * smos_box_vote_dev: smos_box_vote for the `count` frames of a window in one launch, on the first *k_dev boxes:
+ *   host arrays of `count` device pointers / sizes, pose_diff[f] = 16 host doubles or NULL (identity, the current frame).
+ *   counts (device, uint32[max_boxes][3], caller zero-fills).  max_boxes (1..2048) sizes the kernel's LDS.
+ * smos_instance_apply: labels[i] (device int32[n], in place) = 2 if 2 * counts[s][2] > counts[s][1] else 1 for every
+ *   point whose names[i] has a slot s = slot_of[names[i]] < *k_dev (voxel_instance_voting.py:178-183); others are kept.
+ *   max_boxes = rows of counts.
+ */
+int64_t smos_instance_work_bytes(int64_t n);   /* 0 for n <= 0 (or n >= 2^31); needs no device */
+int smos_instance_cluster(const float* pts, int64_t n, int64_t pt_stride, const uint8_t* bf, double eps,
+                          int32_t min_samples, int32_t min_points, float floor_lift, int32_t max_boxes, int32_t* names,
+                          float* boxes, int32_t* slot_of, int32_t* k_dev, int32_t* status, void* work, int64_t work_bytes,
+                          smos_stream_t stream);
+int smos_box_vote_dev(int32_t count, const float* const* pts, const int64_t* n, const int64_t* pt_stride,
+                      const uint8_t* const* labels, const double* const* pose_diff, const float* boxes,
+                      const int32_t* k_dev, int32_t max_boxes, uint32_t* counts, smos_stream_t stream);
+int smos_instance_apply(const int32_t* names, const int32_t* slot_of, const uint32_t* counts, const int32_t* k_dev,
+                        int32_t max_boxes, int32_t* labels, int64_t n, smos_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * Fused point-side kernels of the inference engine (csrc/point_fused.hip).  Scatter targets are
  * channels-last and zero-filled by the caller; features are assumed >= 0 (post-ReLU), as on every call

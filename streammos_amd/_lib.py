@@ -33,6 +33,10 @@ SIGNATURES = {
     "smos_dbscan_work_bytes": [i64],
     "smos_dbscan": [vp, i64, i64, ctypes.c_double, i32, vp, vp, i64, i32, vp],
     "smos_box_vote": [vp, i64, i64, vp, c_f64p, vp, i32, vp, vp],
+    "smos_instance_work_bytes": [i64],
+    "smos_instance_cluster": [vp, i64, i64, vp, ctypes.c_double, i32, i32, ctypes.c_float, i32, vp, vp, vp, vp, vp, vp, i64, vp],
+    "smos_box_vote_dev": [i32, ctypes.POINTER(vp), c_i64p, c_i64p, ctypes.POINTER(vp), ctypes.POINTER(c_f64p), vp, vp, i32, vp, vp],
+    "smos_instance_apply": [vp, vp, vp, vp, i32, vp, i64, vp],
     "smos_pointnet_scatter": [vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, i32, i32, vp],
     "smos_stem_scan_state_words": [i64],
     "smos_stem_mark": [vp, i32, i64, i64, i64, i64, i64, vp, vp, vp],
@@ -119,6 +123,7 @@ def load():
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int
     lib.smos_dbscan_work_bytes.restype = ctypes.c_int64
+    lib.smos_instance_work_bytes.restype = ctypes.c_int64
     lib.smos_stem_scan_state_words.restype = ctypes.c_int64
     lib.smos_conv_cl_sum_chunks.restype = ctypes.c_int64
     lib.smos_conv_wino_sum_chunks.restype = ctypes.c_int64

@@ -336,6 +336,122 @@ def box_vote(points, labels, boxes, counts, pose_diff=None):
     return counts
 
 
+MAX_BOXES = 2048        # upper bound of max_boxes (the LDS of the box vote)
+
+
+def instance_work_bytes(n):
+    """Device scratch smos_instance_cluster needs for a scan of n points (256 bytes of slack for the alignment included)."""
+    need = int(_lib.load().smos_instance_work_bytes(int(n)))
+    if need < 0:
+        raise RuntimeError("instance_cluster: workspace query failed for n=%d" % n)
+    return need + 256
+
+
+def instance_cluster(points, bf, eps, min_samples, min_points, floor_lift, max_boxes=MAX_BOXES, work=None, out=None):
+    """DBSCAN of the scan's foreground points (bf == 2) and the boxes of InstanceVoter.cluster_boxes, with nothing read
+    back.  points [n, >=3] float32 rows (the whole scan), bf [n] uint8.  Returns dict(names int32 [n] (scan index of the
+    cluster's lowest core point; -1 for noise and non-foreground), boxes float32 [max_boxes, 6], slot_of int32 [n] (name ->
+    row of boxes, -1), k int32 [1] (rows used), status int32 [1] (bit 0: more than max_boxes clusters)).  work: a uint8
+    device tensor of >= instance_work_bytes(n) bytes to reuse (its contents do not matter); out: a dict of such tensors
+    to write into."""
+    _require_cuda("instance_cluster", points, bf, work)
+    if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] < 3 or points.stride(1) != 1:
+        raise RuntimeError("instance_cluster: points must be float32 rows [n, >=3]")
+    n = points.shape[0]
+    if bf.dtype != torch.uint8 or bf.dim() != 1 or bf.shape[0] != n or not bf.is_contiguous() or bf.device != points.device:
+        raise RuntimeError("instance_cluster: bf must be a contiguous uint8 [n] tensor on the points' device")
+    max_boxes = int(max_boxes)
+    if not 1 <= max_boxes <= MAX_BOXES:
+        raise RuntimeError("instance_cluster: max_boxes must be in 1..%d, got %d" % (MAX_BOXES, max_boxes))
+    dev = points.device
+    if out is None:
+        out = {"names": torch.empty(n, dtype=torch.int32, device=dev), "slot_of": torch.empty(n, dtype=torch.int32, device=dev),
+               "boxes": torch.empty((max_boxes, 6), dtype=torch.float32, device=dev),
+               "k": torch.empty(1, dtype=torch.int32, device=dev), "status": torch.empty(1, dtype=torch.int32, device=dev)}
+    for key, dtype, numel in (("names", torch.int32, n), ("slot_of", torch.int32, n), ("boxes", torch.float32, max_boxes * 6),
+                              ("k", torch.int32, 1), ("status", torch.int32, 1)):
+        t = out[key]
+        if t.dtype != dtype or t.numel() != numel or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError("instance_cluster: out[%r] must be a contiguous %s tensor of %d elements on the points' device"
+                               % (key, dtype, numel))
+    lib = _lib.load()
+    need = instance_work_bytes(n)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+    base = (work.data_ptr() + 255) // 256 * 256
+    room = work.numel() - (base - work.data_ptr())
+    if work.dtype != torch.uint8 or not work.is_contiguous() or work.device != dev or room < need - 256:
+        raise RuntimeError("instance_cluster: work must be a contiguous uint8 tensor of >= %d bytes on the points' device" % need)
+    with _on(dev), profiling.span_f("instance_cluster[%d]", (n,)):
+        rc = lib.smos_instance_cluster(points.data_ptr(), n, points.stride(0), bf.data_ptr(), float(eps), int(min_samples),
+                                       int(min_points), float(floor_lift), max_boxes, out["names"].data_ptr(),
+                                       out["boxes"].data_ptr(), out["slot_of"].data_ptr(), out["k"].data_ptr(),
+                                       out["status"].data_ptr(), base, room, _stream(points))
+    _lib.check(rc, "smos_instance_cluster")
+    return out
+
+
+def box_vote_dev(frames, boxes, k, counts):
+    """box_vote for a whole window in one launch on the first k[0] rows of boxes, k a DEVICE int32 [1] tensor.  frames: list
+    of (points [n, >=3] float32 rows, labels [n] uint8, pose_diff 4x4 numpy float64 or None).  boxes [max_boxes, 6] float32;
+    counts [max_boxes, 3] uint32/int32, zero-filled by the caller."""
+    _require_cuda("box_vote_dev", boxes, k, counts)
+    if boxes.dtype != torch.float32 or not boxes.is_contiguous() or boxes.dim() != 2 or boxes.shape[1] != 6 \
+            or not 1 <= boxes.shape[0] <= MAX_BOXES:
+        raise RuntimeError("box_vote_dev: boxes must be a contiguous float32 [max_boxes <= %d, 6] tensor" % MAX_BOXES)
+    if counts.dtype not in (torch.int32, torch.uint32) or not counts.is_contiguous() or counts.numel() != boxes.shape[0] * 3:
+        raise RuntimeError("box_vote_dev: counts must be a contiguous 32-bit [max_boxes, 3] tensor")
+    if k.dtype != torch.int32 or k.numel() != 1 or k.device != boxes.device or counts.device != boxes.device:
+        raise RuntimeError("box_vote_dev: k must be an int32 [1] tensor on the boxes' device, counts on it too")
+    if not frames:
+        return counts
+    count = len(frames)
+    pts, lab = (ctypes.c_void_p * count)(), (ctypes.c_void_p * count)()
+    n, stride = (ctypes.c_int64 * count)(), (ctypes.c_int64 * count)()
+    pose = (_lib.c_f64p * count)()
+    keep = []
+    for f, (points, labels, pose_diff) in enumerate(frames):
+        _require_cuda("box_vote_dev", points, labels)
+        if points.dtype != torch.float32 or labels.dtype != torch.uint8 or points.stride(1) != 1 or points.device != boxes.device:
+            raise RuntimeError("box_vote_dev: points must be float32 rows and labels uint8, on the boxes' device")
+        if labels.shape[0] != points.shape[0] or not labels.is_contiguous():
+            raise RuntimeError("box_vote_dev: one contiguous label per point")
+        pts[f], lab[f], n[f], stride[f] = points.data_ptr(), labels.data_ptr(), points.shape[0], points.stride(0)
+        if pose_diff is not None:
+            arr = np.ascontiguousarray(pose_diff, dtype=np.float64).reshape(-1)
+            if arr.size < 16:
+                raise RuntimeError("box_vote_dev: pose_diff must be 4x4")
+            keep.append(arr)                          # the numpy buffer is read during the call
+            pose[f] = arr.ctypes.data_as(_lib.c_f64p)
+    lib = _lib.load()
+    with _on(boxes.device), profiling.span_f("box_vote_dev[%dx%d]", (count, max(n))):
+        rc = lib.smos_box_vote_dev(count, pts, n, stride, lab, pose, boxes.data_ptr(), k.data_ptr(), boxes.shape[0],
+                                   counts.data_ptr(), _stream(boxes))
+    _lib.check(rc, "smos_box_vote_dev")
+    return counts
+
+
+def instance_apply(names, slot_of, counts, k, labels):
+    """labels (int32 [n], in place): 2 if 2 * counts[s, 2] > counts[s, 1] else 1 for every point whose cluster names[i] has
+    a slot s = slot_of[names[i]] (voxel_instance_voting.py:178-183); every other label is kept."""
+    _require_cuda("instance_apply", names, slot_of, counts, k, labels)
+    n = labels.shape[0]
+    for what, t in (("names", names), ("slot_of", slot_of), ("labels", labels)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous() or t.device != labels.device:
+            raise RuntimeError("instance_apply: %s must be a contiguous int32 [n] tensor on the labels' device" % what)
+    if counts.dtype not in (torch.int32, torch.uint32) or not counts.is_contiguous() or counts.dim() != 2 or counts.shape[1] != 3 \
+            or counts.device != labels.device:
+        raise RuntimeError("instance_apply: counts must be a contiguous 32-bit [max_boxes, 3] tensor on the labels' device")
+    if k.dtype != torch.int32 or k.numel() != 1 or k.device != labels.device:
+        raise RuntimeError("instance_apply: k must be an int32 [1] tensor on the labels' device")
+    lib = _lib.load()
+    with _on(labels.device):
+        rc = lib.smos_instance_apply(names.data_ptr(), slot_of.data_ptr(), counts.data_ptr(), k.data_ptr(), counts.shape[0],
+                                     labels.data_ptr(), n, _stream(labels))
+    _lib.check(rc, "smos_instance_apply")
+    return labels
+
+
 def _label_args(name, words, gt, gt_map, counts, n, device):
     """Checks shared by label_words / voted_label_counts; returns the raw pointers (None where absent)."""
     _require_cuda(name, words, gt, gt_map, counts)

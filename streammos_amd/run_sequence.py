@@ -122,13 +122,17 @@ def _run_overlapped(model, seq_dir, out_dir, files, poses, has_gt, device, vote,
     the frame's device staging slot, copies the window's in-range counts there and queues one device-to-host copy of the
     slot on a copy stream; the writer thread waits for that copy, checks the counts (the host path's capacity error) and
     writes the files.  Nothing is read back per frame: the one wait is for a free output slot, IN_FLIGHT frames behind.
-    The IoU counters are read once, at the end.  Instance voting (vote="instance") still synchronises inside the voter
-    (ops.dbscan, the cluster tests of InstanceVoter.cluster_boxes)."""
+    The IoU counters are read once, at the end.  Instance voting (vote="instance") runs the voter's device-resident path
+    (SMOS_INSTANCE_DEVICE=0: the path that reads back per voted frame): the status word of every voted frame travels in the
+    slot, and the writer raises before that frame's refined file if the frame had more clusters than the voter has boxes."""
     from . import ops, sequence_io
     from .device_preprocess import check_in_range_counts
     device = torch.device(device)
     n = len(files)
-    runner = streaming.StreamRunner(model, device, vote=vote, pipeline=True)
+    runner = streaming.StreamRunner(model, device, vote=vote, pipeline=True,
+                                    instance_device=streaming.instance_device_switch(True))
+    voter = runner.voter
+    voter_status = voter.status if isinstance(voter, streaming.InstanceVoter) and voter.device_resident else None
     main = torch.cuda.current_stream(device)
     copier = torch.cuda.Stream(device)
     gt_map = torch.from_numpy(kitti.learning_map_lut()).to(device)
@@ -138,7 +142,7 @@ def _run_overlapped(model, seq_dir, out_dir, files, poses, has_gt, device, vote,
     writer = None
     try:
         a4 = (reader.max_points + 3) // 4 * 4
-        cap = (2 + streaming.VOTE_WINDOW) * a4 + (seq_num + 3) // 4 * 4
+        cap = (2 + streaming.VOTE_WINDOW) * a4 + (seq_num + 3) // 4 * 4 + 4 * streaming.VOTE_WINDOW
         dev_stage = [torch.empty(cap, dtype=torch.int32, device=device) for _ in range(IN_FLIGHT)]
         host_stage = [torch.empty(cap, dtype=torch.int32, pin_memory=True) for _ in range(IN_FLIGHT)]
         writer = sequence_io.SlotWriter(range(IN_FLIGHT))
@@ -184,6 +188,8 @@ def _run_overlapped(model, seq_dir, out_dir, files, poses, has_gt, device, vote,
                 raise RuntimeError("run_sequence: the voter released %d frames at once (slots hold %d)"
                                    % (len(voted), streaming.VOTE_WINDOW))
             for fid, lab in voted:
+                if voter_status is not None:          # checked by the writer before the frame's refined file
+                    section(("status", fid), 1).copy_(voter_status(fid))
                 ops.voted_label_counts(lab, gt_dev.pop(fid) if has_gt else None, gt_map, counts_ref,
                                        words=section(("refined", fid), lab.shape[0]))
             ready = torch.cuda.Event()
@@ -202,6 +208,11 @@ def _run_overlapped(model, seq_dir, out_dir, files, poses, has_gt, device, vote,
                 for key, (o, m) in parts.items():
                     if key != "counts":
                         sub, fid = key
+                        if sub == "status":
+                            if int(host[o]) & 1:
+                                raise RuntimeError("instance voting: more than %d clusters in frame %s"
+                                                   % (voter.max_boxes, files[fid][:-4]))
+                            continue
                         kitti.write_prediction(os.path.join(out_dir, sub, files[fid][:-4] + ".label"), lut_labels=host[o:o + m])
 
             writer.submit(k, copied, write)

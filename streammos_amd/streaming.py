@@ -10,6 +10,7 @@ Sequences are independent streams: multi-GPU inference as
 ranks (``shard_sequences``) and needs no collective.
 """
 import collections
+import os
 
 import numpy as np
 import torch
@@ -105,17 +106,38 @@ class InstanceVoter(VoxelVoter):
     class-2 points of the local map inside each box are counted on the device (ops.box_vote; the local map is the
     pose-aligned, cropped window with its PRE-vote predictions) and every point of the cluster takes class 2 if
     2 * n2 > n1 (the reference sums label VALUES, :178-179) else class 1.  torch is used for the small bookkeeping in
-    between (compaction, per-cluster min / max); the DBSCAN call synchronises the stream."""
+    between (compaction, per-cluster min / max); the DBSCAN call synchronises the stream.
+
+    device_resident=True: the same vote as a fixed sequence of launches (ops.instance_cluster, ops.box_vote_dev,
+    ops.instance_apply) -- the foreground count, the clusters and their boxes never leave the device, nothing is read back
+    and no branch depends on the data; a frame without foreground or without a kept cluster runs the same launches as
+    no-ops.  At most max_boxes clusters per frame get a box; a frame with more sets bit 0 of its status word
+    (``status(frame_id)``, a device tensor) and votes on max_boxes of them."""
 
     EPS, MIN_SAMPLES, MIN_POINTS, FLOOR_LIFT = 0.3, 5, 30, 0.2
+    MAX_BOXES = ops.MAX_BOXES           # max_boxes of a voter that is not given one (2048, the upper bound)
 
-    def __init__(self, device, window=VOTE_WINDOW, lut=LEARNING_MAP_INV, recip_quantize=False):
+    def __init__(self, device, window=VOTE_WINDOW, lut=LEARNING_MAP_INV, recip_quantize=False, device_resident=False,
+                 max_boxes=None):
         super().__init__(device, window=window, lut=lut, recip_quantize=recip_quantize)
         self.bf = {}
+        self.device_resident = bool(device_resident)
+        self.max_boxes = int(self.MAX_BOXES if max_boxes is None else max_boxes)
+        if not 1 <= self.max_boxes <= ops.MAX_BOXES:
+            raise ValueError("max_boxes must be in 1..%d, got %d" % (ops.MAX_BOXES, self.max_boxes))
+        self._status = {}               # frame_id -> int32 [1] device tensor (device_resident)
+        self._cap = 0                   # largest scan seen: the scratch below is allocated for it
+        self._scratch = None
 
     def reset(self):
         super().reset()
         self.bf.clear()
+        self._status.clear()
+
+    def status(self, frame_id):
+        """The status word of a voted frame (int32 [1] device tensor; bit 0: more than max_boxes clusters).  Kept as long as
+        the frame is in the window."""
+        return self._status[frame_id]
 
     def push(self, points, preds, pose, bf=None):
         if bf is None:
@@ -124,6 +146,8 @@ class InstanceVoter(VoxelVoter):
         ready = super().push(points, preds, pose)
         for k in [k for k in self.bf if k not in self.frames]:
             del self.bf[k]
+        for k in [k for k in self._status if k not in self.frames]:
+            del self._status[k]
         return ready
 
     def cluster_boxes(self, fpts):
@@ -155,14 +179,41 @@ class InstanceVoter(VoxelVoter):
         slot[valid] = slot_of[inv]
         return slot >= 0, slot, boxes.contiguous()
 
+    def _buffers(self, n):
+        """Scratch of the device-resident path, allocated once for the largest scan seen (n is host knowledge)."""
+        if self._scratch is None or n > self._cap:
+            self._cap = max(n, self._cap)
+            i32 = dict(dtype=torch.int32, device=self.device)
+            self._scratch = {"work": torch.empty(ops.instance_work_bytes(self._cap), dtype=torch.uint8, device=self.device),
+                             "names": torch.empty(self._cap, **i32), "slot_of": torch.empty(self._cap, **i32),
+                             "boxes": torch.empty((self.max_boxes, 6), dtype=torch.float32, device=self.device),
+                             "k": torch.empty(1, **i32), "counts": torch.empty((self.max_boxes, 3), **i32)}
+        return self._scratch
+
+    def _vote_device(self, fid, window, labels):
+        pts, bf = self.frames[fid][0], self.bf[fid]
+        n = pts.shape[0]
+        buf = self._buffers(n)
+        status = torch.empty(1, dtype=torch.int32, device=self.device)
+        self._status[fid] = status
+        out = {"names": buf["names"][:n], "slot_of": buf["slot_of"][:n], "boxes": buf["boxes"], "k": buf["k"], "status": status}
+        ops.instance_cluster(pts, bf, self.EPS, self.MIN_SAMPLES, self.MIN_POINTS, self.FLOOR_LIFT, self.max_boxes,
+                             work=buf["work"], out=out)
+        buf["counts"].zero_()
+        ops.box_vote_dev(window, buf["boxes"], buf["k"], buf["counts"])
+        ops.instance_apply(out["names"], out["slot_of"], buf["counts"], buf["k"], labels)
+
     def _vote(self, fid):
         pts, pred, pose = self.frames[fid]
         inv_cur = np.linalg.inv(pose)
         history = [(h, inv_cur.dot(self.frames[h][2])) for h in vote_history_ids(fid, self.window) if h in self.frames]
+        window = [(self.frames[h][0], self.frames[h][1], diff) for h, diff in history] + [(pts, pred, None)]
         ops.vote_clear(self.table)
-        ops.vote_accumulate_frames([(self.frames[h][0], self.frames[h][1], diff) for h, diff in history] + [(pts, pred, None)],
-                                   self.table, recip_quantize=self.recip)
+        ops.vote_accumulate_frames(window, self.table, recip_quantize=self.recip)
         labels = ops.vote_resolve(pts, pred, self.table, lut=None, recip_quantize=self.recip)
+        if self.device_resident:
+            self._vote_device(fid, window, labels)
+            return self.lut[labels.long()] if self.lut is not None else labels
         fg = torch.nonzero(self.bf[fid] == 2).flatten()                   # :145
         if fg.numel() > 0:
             member, slot, boxes = self.cluster_boxes(pts[fg][:, :3].contiguous())
@@ -174,6 +225,13 @@ class InstanceVoter(VoxelVoter):
                 verdict = torch.where(2 * counts[:, 2] > counts[:, 1], 2, 1).to(torch.int32)   # :178-183
                 labels[fg[member]] = verdict[slot[member]]
         return self.lut[labels.long()] if self.lut is not None else labels
+
+
+def instance_device_switch(default):
+    """The A/B switch SMOS_INSTANCE_DEVICE (1: device-resident instance voting, 0: the path that reads back per frame);
+    `default` when it is unset."""
+    value = os.environ.get("SMOS_INSTANCE_DEVICE", "")
+    return bool(default) if value == "" else value != "0"
 
 
 def concurrent_stream(device, candidates=8, spin_cycles=400000):
@@ -226,19 +284,23 @@ class StreamRunner:
     """infer -> TTA reduce -> labels for the raw scan -> voxel voting, all on one device, one stream."""
 
     def __init__(self, model, device="cuda:0", vote=True, recip_quantize=False, graph=False, split=1, pipeline=False,
-                 skip_padding=True, conv_precision=None):
+                 skip_padding=True, conv_precision=None, instance_device=None):
         """graph=True captures the network forward of a frame into hipGraphs (first frame: learned memory embedding;
         later frames: recurrent memory) that are replayed on static buffers -- one launch per scan instead of ~180.
         split=k additionally cuts the TTA batch into k independent groups (TTA variants never interact inside the
         network) whose graphs are replayed on k HIP streams at once, so that the many small kernels of one group fill
         the CUs the other group leaves idle.  Voting stays outside the graphs (pose matrices are launch arguments).
-        conv_precision "fp32" / "bf16": sets model.engine_conv_precision (None: the model's setting, "fp32" by default)."""
+        conv_precision "fp32" / "bf16": sets model.engine_conv_precision (None: the model's setting, "fp32" by default).
+        instance_device (vote="instance"): the voter's device-resident path, InstanceVoter(device_resident=True); None reads
+        the A/B switch SMOS_INSTANCE_DEVICE (0 when unset)."""
         self.device = torch.device(device)
         self.model = model.to(self.device).eval()
         set_conv_precision(self.model, conv_precision)
         # vote: False / True (voxel voting) / "instance" (voxel + instance voting; needs the StreamMOS_seg model)
         if vote == "instance":
-            self.voter = InstanceVoter(self.device, recip_quantize=recip_quantize)
+            if instance_device is None:
+                instance_device = instance_device_switch(False)
+            self.voter = InstanceVoter(self.device, recip_quantize=recip_quantize, device_resident=instance_device)
         else:
             self.voter = VoxelVoter(self.device, recip_quantize=recip_quantize) if vote else None
         self.use_graph = graph

@@ -5,6 +5,10 @@ frame_point_num 160000), stage-2 model + instance voting; prints the IoU report 
     python tools/e2e_sequence.py --steady N   # stage 1 + voxel voting + --device-preprocess on N >= 200 scans: a warm-up
                                               # run, then a second run_sequence call on the same model (warm page cache)
                                               # timed on its own: steady-state scans/s of the deployable loop
+    python tools/e2e_sequence.py --steady N --instance [--alternate R]
+                                              # the steady mode with the stage-2 model and instance voting (vote="instance",
+                                              # device preprocessing); --alternate R: after the warm-up runs, R timed runs
+                                              # each with SMOS_INSTANCE_DEVICE=0 and =1, alternating, in this process
     --conv-precision {fp32,bf16}              # the engine's convolution precision (default fp32)
 """
 import os, sys, tempfile, time
@@ -19,7 +23,13 @@ if "--conv-precision" in sys.argv:
     if prec not in ("fp32", "bf16"):
         sys.exit("--conv-precision: fp32 or bf16")
     del sys.argv[i:i + 2]
-args = [a for a in sys.argv[1:] if a != "--steady"]
+instance = "--instance" in sys.argv
+alternate = 0
+if "--alternate" in sys.argv:
+    i = sys.argv.index("--alternate")
+    alternate = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+args = [a for a in sys.argv[1:] if a not in ("--steady", "--instance")]
 n = int(args[0]) if args else (200 if steady else 24)
 root = tempfile.mkdtemp(prefix="smos_seq_")
 seq = os.path.join(root, "sequences", "08")
@@ -32,16 +42,23 @@ kitti.write_poses(os.path.join(seq, "poses.txt"), [synth.synthetic_pose(k) for k
 kitti.write_calibration(os.path.join(seq, "calib.txt"))
 if steady:
     import torch
-    model = run_sequence.load_model(None, "cuda:0")
-    for rep in ("warm-up", "timed"):
+    model = run_sequence.load_model(None, "cuda:0", seg=instance)
+    what = "stage 2 + instance voting" if instance else "stage 1 + voxel voting"
+    reps = [("warm-up", None), ("timed", None)]
+    if instance and alternate:
+        reps = [("warm-up", "0"), ("warm-up", "1")] + [("timed", v) for _ in range(alternate) for v in ("0", "1")]
+    for rep, switch in reps:
+        if switch is not None:
+            os.environ["SMOS_INSTANCE_DEVICE"] = switch
         torch.cuda.synchronize()
         t = time.perf_counter()
-        res = run_sequence.run_sequence(model, seq, os.path.join(root, "out_steady"), "cuda:0", vote=True, device_preprocess=True,
-                                        conv_precision=prec)
+        res = run_sequence.run_sequence(model, seq, os.path.join(root, "out_steady"), "cuda:0", vote="instance" if instance else True,
+                                        device_preprocess=True, conv_precision=prec)
         torch.cuda.synchronize()          # run_sequence returns after its last file is written; nothing is left queued
         dt = time.perf_counter() - t
-        print("steady %s (conv %s): stage 1 + voxel voting + device preprocessing, %d scans: %.1f scans/s (%.2f ms/scan, disk IO "
-              "and runner set-up included)" % (rep, prec, n, n / dt, 1e3 * dt / n), res, flush=True)
+        tag = " SMOS_INSTANCE_DEVICE=%s" % os.environ.get("SMOS_INSTANCE_DEVICE", "unset") if instance else ""
+        print("steady %s (conv %s%s): %s + device preprocessing, %d scans: %.1f scans/s (%.2f ms/scan, disk IO "
+              "and runner set-up included)" % (rep, prec, tag, what, n, n / dt, 1e3 * dt / n), res, flush=True)
     sys.exit(0)
 for seg, vote, devpre in ((False, True, False), (True, "instance", False), (True, "instance", True)):
     model = run_sequence.load_model(None, "cuda:0", seg=seg)
