@@ -89,6 +89,19 @@ int smos_bilinear_gather_fwd(const float* grid, const int64_t* grid_stride, cons
                              float* out, const int64_t* out_stride, int64_t B, int64_t C, int64_t H,
                              int64_t W, int64_t N, const float* scale, smos_stream_t stream);
 
+/* Its gradient with respect to grid: grad_grid[b, c, y, x] = sum over the points and their four taps of
+ * w_tap * grad_out[b, c, n], with the taps, weights and range rules of the forward (a tap outside the map, a NaN
+ * coordinate or a padding row adds nothing).  There is no gradient with respect to coord.  Float32 only.
+ *   grad_out  [B, C, N]     element strides grad_out_stride[3]   (channel-major or point-major)
+ *   coord     [B, N, K]     contiguous, as in the forward
+ *   grad_grid [B, C, H, W]  element strides grad_grid_stride[4]; may arrive uninitialised: the call zeroes it itself.
+ * A destination with channel stride 1 (channels-last) and C >= 8 is added to in whole row segments; any other takes
+ * one 4-byte atomic per (point, tap, channel).  The sums depend on the arrival order of the atomics.
+ */
+int smos_bilinear_gather_bwd(const float* grad_out, const int64_t* grad_out_stride, const float* coord, int32_t K,
+                             float* grad_grid, const int64_t* grad_grid_stride, int64_t B, int64_t C, int64_t H,
+                             int64_t W, int64_t N, const float* scale, smos_stream_t stream);
+
 /* --------------------------------------------------------------------------------------------
  * Multi-scale deformable attention sampler, forward.
  * Replaces MultiScaleDeformableAttention.ms_deform_attn_forward (deformattn/src/vision.cpp:13-16 ->

@@ -4,6 +4,12 @@
 // un-normalise round trip of that formulation is reproduced operation by operation (__f*_rn
 // intrinsics, so the compiler neither contracts nor reassociates it): the sampling position then
 // matches the reference's to the last bit and only the four-tap blend differs by FMA rounding.
+//
+// Backward (smos_bilinear_gather_bwd): grad_grid += w_k * grad_out over the same four taps, taken from the same make_taps.
+// Main form bil_bwd_rows: channels-last destination, lane = channel, so one atomic wave-instruction adds one contiguous
+// row segment (the shape at which MI355X's memory-side float atomics reach their chip-wide rate); runs of consecutive
+// points in one cell are summed in registers first.  Fallback bil_bwd_points: lane = point, 4-byte atomics at any strides.
+// The sums depend on the arrival order of the atomics: last bits can differ from run to run.
 #include "smos_common.h"
 
 namespace smos {
@@ -18,6 +24,7 @@ struct BilGeom {
 struct Taps {
   int64_t o[4];
   float w[4];
+  int y0, x0;  // cell of the north-west tap (-5, -5: not a finite position near the map)
 };
 
 // pixel position exactly as backbone.py:467-468 + ATen's grid_sampler_unnormalize(align_corners=True)
@@ -49,6 +56,8 @@ __device__ __forceinline__ Taps make_taps(const float* __restrict__ crow, const 
     t.o[k] = in ? (int64_t)y * g.gs_h + (int64_t)x * g.gs_w : (int64_t)-1;
     if (!in) t.w[k] = 0.0f;
   }
+  t.y0 = y0;
+  t.x0 = x0;
   return t;
 }
 
@@ -100,6 +109,144 @@ __global__ __launch_bounds__(kBlock) void bil_rows(const float* __restrict__ gri
   }
 }
 
+
+// ---- backward ----
+constexpr int kBt = 32;      // points per wave tile
+constexpr int kBPitch = 66;  // floats per LDS row: the fill's lane (p, h) writes bank (2 p + 2 j + h) mod 64, all different
+
+__device__ __forceinline__ void bwd_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ float lane_f(float v, int i) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i));
+}
+
+// lane = point, loop over channels: 4-byte atomics at the destination's strides (C < 8, or a destination that is not
+// channels-last).  BilGeom: gs_* = grad_grid strides, os_* = grad_out strides.  The trip count is the same for every
+// lane; a lane past the end works on the last point (clamped address) and its adds are masked: no load sits under a
+// lane-dependent branch.
+__global__ __launch_bounds__(kBlock) void bil_bwd_points(const float* __restrict__ gout, const float* __restrict__ coord,
+                                                         float* __restrict__ ggrid, BilGeom g, int64_t B, int64_t C,
+                                                         int64_t N) {
+  const int64_t total = B * N;
+  for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < total; base += (int64_t)gridDim.x * blockDim.x) {
+    const bool has = base + threadIdx.x < total;
+    const int64_t i = has ? base + threadIdx.x : total - 1;
+    const int64_t b = i / N, n = i - b * N;
+    const Taps t = make_taps(coord + i * g.K, g);
+    const float* __restrict__ gp = gout + b * g.os_b + n * g.os_n;
+    float* __restrict__ db = ggrid + b * g.gs_b;
+    for (int64_t c = 0; c < C; ++c) {
+      const float x = gp[c * g.os_c];
+      float* dc = db + c * g.gs_c;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (has && t.o[k] >= 0) atomicAdd(dc + t.o[k], t.w[k] * x);
+    }
+  }
+}
+
+// A wave owns tiles of kBt consecutive points of one sample.  Lane = point prepares the taps once per tile; then, per chunk
+// of 64 channels, lane = channel walks the tile's points: the weights and the cell come from the point's lane by
+// v_readlane (wave-uniform), runs of points in one cell are summed in registers, and a run ends with up to four row atomics.
+// kStage: grad_out is channel-major, so the tile goes through wave-private LDS (filled along n, read out along c);
+// otherwise (stride_c == 1) the rows are read directly.  Every load is unconditional: a lane without a point or a channel
+// reads a clamped address and its value is dropped by a select.
+template <bool kStage>
+__global__ __launch_bounds__(kBlock) void bil_bwd_rows(const float* __restrict__ gout, const float* __restrict__ coord,
+                                                       float* __restrict__ ggrid, BilGeom g, int64_t B, int64_t C,
+                                                       int64_t N) {
+  __shared__ float lds[kStage ? kBlock / kWave : 1][kStage ? kBt * kBPitch : 1];
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  const int p = lane & (kBt - 1), hh = lane >> 5;
+  float* tile = lds[kStage ? wave : 0];
+  const int64_t tiles_per = (N + kBt - 1) / kBt, n_tiles = B * tiles_per;
+  constexpr int kWaves = kBlock / kWave;
+  for (int64_t tl = (int64_t)blockIdx.x * kWaves + wave; tl < n_tiles; tl += (int64_t)gridDim.x * kWaves) {
+    const int64_t b = tl / tiles_per, n0 = (tl - b * tiles_per) * kBt;
+    const int n_valid = (int)min((int64_t)kBt, N - n0);
+    const bool has = p < n_valid;
+    const int64_t np = n0 + (has ? p : 0);
+    Taps t = make_taps(coord + (b * N + np) * g.K, g);
+    if (!has) {
+      t.y0 = -5;
+      t.x0 = -5;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) t.w[k] = 0.0f;
+    }
+    const bool any = has && (t.o[0] >= 0 || t.o[1] >= 0 || t.o[2] >= 0 || t.o[3] >= 0);
+    if (__ballot(any) == 0) continue;      // padding tail of a scan: nothing to add
+    // the shuffles are their own statements (inside a short-circuit expression they would run with lanes masked off)
+    const int y_after = __shfl_down(t.y0, 1), x_after = __shfl_down(t.x0, 1);
+    const uint32_t tails = (uint32_t)__ballot(hh == 0 && (p == kBt - 1 || t.y0 != y_after || t.x0 != x_after));
+    for (int64_t c0 = 0; c0 < C; c0 += kWave) {
+      const int cn = (int)min((int64_t)kWave, C - c0);
+      const bool chan = lane < cn;
+      float v[kBt];
+      if (kStage) {
+        const float* __restrict__ src = gout + b * g.os_b + np * g.os_n + c0 * g.os_c;
+        const int jn = (cn + 1) >> 1;
+#pragma unroll 8
+        for (int j = 0; j < jn; ++j) {
+          const int c = 2 * j + hh;
+          const float x = src[(int64_t)(c < cn ? c : 0) * g.os_c];
+          tile[p * kBPitch + c] = has ? x : 0.0f;
+        }
+        bwd_wave_sync();
+        // a lane >= cn reads columns this chunk never filled: whatever it sums is dropped by `chan` at the atomics
+#pragma unroll
+        for (int i = 0; i < kBt; ++i) v[i] = tile[i * kBPitch + lane];
+        bwd_wave_sync();
+      } else {
+        const float* __restrict__ src = gout + b * g.os_b + c0 + (chan ? lane : 0);
+#pragma unroll
+        for (int i = 0; i < kBt; ++i) {
+          const float x = src[(n0 + (i < n_valid ? i : 0)) * g.os_n];
+          v[i] = i < n_valid ? x : 0.0f;
+        }
+      }
+      float* __restrict__ dst = ggrid + b * g.gs_b + c0 + lane;
+      // A tap outside the map (weight zeroed) is outside for the whole run, since a run is one cell: if a non-finite
+      // grad_out turns 0 * v into NaN there, that acc[k] is never added anywhere and is reset with the run.
+      float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int i = 0; i < kBt; ++i) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = fmaf(lane_f(t.w[k], i), v[i], acc[k]);
+        if ((tails >> i) & 1) {
+          const int yi = __builtin_amdgcn_readlane(t.y0, i), xi = __builtin_amdgcn_readlane(t.x0, i);
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int y = yi + (k >> 1), x = xi + (k & 1);
+            if (y >= 0 && y < g.H && x >= 0 && x < g.W && chan) atomicAdd(dst + (int64_t)y * g.gs_h + (int64_t)x * g.gs_w, acc[k]);
+            acc[k] = 0.0f;
+          }
+        }
+      }
+    }
+  }
+}
+
+// zero fill of a destination that is not one dense block: dims sorted by stride, the smallest last
+struct ZeroGeom {
+  int64_t size[4], stride[4];
+};
+__global__ __launch_bounds__(kBlock) void bil_bwd_zero(float* __restrict__ p, ZeroGeom z, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t r = i, off = 0;
+#pragma unroll
+    for (int d = 3; d >= 0; --d) {
+      const int64_t q = r / z.size[d];
+      off += (r - q * z.size[d]) * z.stride[d];
+      r = q;
+    }
+    p[off] = 0.0f;
+  }
+}
+
 }  // namespace smos
 
 using namespace smos;
@@ -141,4 +288,61 @@ extern "C" int smos_bilinear_gather_fwd(const float* grid, const int64_t* grid_s
                        out, g, B, C, N, c_chunk);
   }
   return check_launch("bilinear_gather_fwd");
+}
+
+extern "C" int smos_bilinear_gather_bwd(const float* grad_out, const int64_t* grad_out_stride, const float* coord, int32_t K,
+                                        float* grad_grid, const int64_t* grad_grid_stride, int64_t B, int64_t C, int64_t H,
+                                        int64_t W, int64_t N, const float* scale, smos_stream_t stream) {
+  SMOS_REQUIRE(B >= 0 && C >= 0 && N >= 0 && H > 0 && W > 0, "bilinear_gather_bwd: bad sizes");
+  SMOS_REQUIRE(H < (1 << 24) && W < (1 << 24), "bilinear_gather_bwd: grid too large");
+  SMOS_REQUIRE(K >= 2, "bilinear_gather_bwd: coord needs >= 2 columns, got %d", (int)K);
+  if (B == 0 || C == 0) return SMOS_OK;
+  SMOS_REQUIRE(grad_grid && grad_grid_stride, "bilinear_gather_bwd: null pointer");
+  BilGeom g;
+  g.gs_b = grad_grid_stride[0]; g.gs_c = grad_grid_stride[1]; g.gs_h = grad_grid_stride[2]; g.gs_w = grad_grid_stride[3];
+  hipStream_t s = (hipStream_t)stream;
+
+  // the destination arrives uninitialised: one dense block is a memset, anything else a strided fill
+  ZeroGeom z;
+  const int64_t size[4] = {B, C, H, W};
+  int order[4] = {0, 1, 2, 3};
+  for (int i = 1; i < 4; ++i)
+    for (int j = i; j > 0 && grad_grid_stride[order[j]] > grad_grid_stride[order[j - 1]]; --j) {
+      const int tmp = order[j]; order[j] = order[j - 1]; order[j - 1] = tmp;
+    }
+  bool dense = true;
+  int64_t expect = 1;
+  for (int d = 3; d >= 0; --d) {
+    z.size[d] = size[order[d]];
+    z.stride[d] = grad_grid_stride[order[d]];
+    SMOS_REQUIRE(z.stride[d] >= 0, "bilinear_gather_bwd: negative destination stride");
+    if (z.size[d] > 1) {
+      dense = dense && z.stride[d] == expect;
+      expect *= z.size[d];
+    }
+  }
+  const int64_t total = B * C * H * W;
+  if (dense) {
+    if (hipMemsetAsync(grad_grid, 0, (size_t)total * sizeof(float), s) != hipSuccess) return check_launch("bilinear_gather_bwd memset");
+  } else {
+    hipLaunchKernelGGL(bil_bwd_zero, dim3(grid_for(total, kBlock, 256 * 16)), dim3(kBlock), 0, s, grad_grid, z, total);
+    const int rc = check_launch("bilinear_gather_bwd zero");
+    if (rc != SMOS_OK) return rc;
+  }
+  if (N == 0) return SMOS_OK;
+  SMOS_REQUIRE(grad_out && coord && grad_out_stride && scale, "bilinear_gather_bwd: null pointer");
+  g.os_b = grad_out_stride[0]; g.os_c = grad_out_stride[1]; g.os_n = grad_out_stride[2];
+  g.H = (int)H; g.W = (int)W; g.K = K; g.sy = scale[0]; g.sx = scale[1];
+  if (g.gs_c == 1 && C >= 8) {
+    const int64_t tiles = B * ((N + kBt - 1) / kBt);
+    const dim3 gr(grid_for(tiles, kBlock / kWave, kMaxGrid));
+    if (g.os_c == 1)
+      hipLaunchKernelGGL((bil_bwd_rows<false>), gr, dim3(kBlock), 0, s, grad_out, coord, grad_grid, g, B, C, N);
+    else
+      hipLaunchKernelGGL((bil_bwd_rows<true>), gr, dim3(kBlock), 0, s, grad_out, coord, grad_grid, g, B, C, N);
+  } else {
+    hipLaunchKernelGGL(bil_bwd_points, dim3(grid_for(B * N, kBlock, 256 * 16)), dim3(kBlock), 0, s, grad_out, coord, grad_grid,
+                       g, B, C, N);
+  }
+  return check_launch("bilinear_gather_bwd");
 }

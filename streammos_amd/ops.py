@@ -142,12 +142,7 @@ def voxel_maxpool_bwd(feat, ind, out, grad_out, grad_feat, out_size, scale):
     return grad_feat
 
 
-def bilinear_gather(grid, coord, scale, out=None, point_major=False):
-    """grid [B,C,H,W] (any strides), coord [B,N,K(,1)] -> out [B,C,N] (a view of a [B,N,C] buffer when
-    point_major)."""
-    _require_cuda("bilinear_gather", grid, coord, out)
-    if grid.dtype != torch.float32 or coord.dtype != torch.float32:
-        raise RuntimeError("bilinear_gather: float32 only (got %s, %s)" % (grid.dtype, coord.dtype))
+def _bilinear_gather_fwd(grid, coord, scale, out, point_major):
     if coord.dim() == 4:
         coord = coord[..., 0]
     if not coord.is_contiguous():
@@ -166,6 +161,75 @@ def bilinear_gather(grid, coord, scale, out=None, point_major=False):
                                           _lib.f32_array(scale), _stream(grid))
     _lib.check(rc, "smos_bilinear_gather_fwd")
     return out
+
+
+def bilinear_gather_backward(grad_out, coord, scale, grid_shape, channels_last=True):
+    """Gradient of ``bilinear_gather`` with respect to its grid (csrc/bilinear_gather.hip, smos_bilinear_gather_bwd).
+
+    grad_out [B,C,N] (any strides: channel-major from the module graph, point-major from a point-major forward),
+    coord [B,N,K(,1)], grid_shape (B,C,H,W) or (H,W) -> grad_grid [B,C,H,W].  With ``channels_last`` the result is a
+    permuted view of a [B,H,W,C] buffer, which the kernel adds to in whole rows; otherwise it is NCHW-contiguous and
+    every (point, tap, channel) is a 4-byte atomic.  The kernel zeroes the result itself.  The sums are float atomics:
+    their last bits depend on arrival order."""
+    _require_cuda("bilinear_gather_backward", grad_out, coord)
+    if grad_out.dtype != torch.float32 or coord.dtype != torch.float32:
+        raise RuntimeError("bilinear_gather_backward: float32 only (got %s, %s)" % (grad_out.dtype, coord.dtype))
+    if coord.dim() == 4:
+        coord = coord[..., 0]
+    if grad_out.dim() == 4:
+        grad_out = grad_out[..., 0]
+    if not coord.is_contiguous():
+        coord = coord.contiguous()
+    b, c, n = grad_out.shape
+    h, w = int(grid_shape[-2]), int(grid_shape[-1])
+    k = coord.shape[2]
+    if coord.shape[0] != b or coord.shape[1] != n or (len(grid_shape) == 4 and (int(grid_shape[0]), int(grid_shape[1])) != (b, c)):
+        raise RuntimeError("bilinear_gather_backward: shape mismatch grad_out %s coord %s grid %s"
+                           % (tuple(grad_out.shape), tuple(coord.shape), tuple(grid_shape)))
+    if channels_last:
+        grad_grid = torch.empty((b, h, w, c), dtype=torch.float32, device=grad_out.device).permute(0, 3, 1, 2)
+    else:
+        grad_grid = torch.empty((b, c, h, w), dtype=torch.float32, device=grad_out.device)
+    lib = _lib.load()
+    with _on(grad_out.device), profiling.span_f("bilinear_gather_bwd[%dx%dx%dx%d<-%d]", (b, c, h, w, n)):
+        rc = lib.smos_bilinear_gather_bwd(grad_out.data_ptr(), _lib.i64_array(grad_out.stride()), coord.data_ptr(), k,
+                                          grad_grid.data_ptr(), _lib.i64_array(grad_grid.stride()), b, c, h, w, n,
+                                          _lib.f32_array(scale), _stream(grad_out))
+    _lib.check(rc, "smos_bilinear_gather_bwd")
+    return grad_grid
+
+
+class _BilinearGather(torch.autograd.Function):
+    """bilinear_gather, differentiable in grid.  ``out`` travels inside a tuple: autograd then sees no tensor that is both an
+    input and modified, and the result is an alias of it that carries the graph."""
+
+    @staticmethod
+    def forward(ctx, grid, coord, scale, out_box, point_major):
+        ctx.save_for_backward(coord)
+        ctx.scale, ctx.grid_shape = tuple(float(v) for v in scale), tuple(grid.shape)
+        res = _bilinear_gather_fwd(grid, coord, scale, out_box[0], point_major)
+        return res.detach() if out_box[0] is not None else res
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        coord, = ctx.saved_tensors
+        # handed on channels-last-strided, as written: an NCHW copy made the training step longer (DESIGN.md 4.2)
+        return bilinear_gather_backward(grad_out, coord, ctx.scale, ctx.grid_shape, channels_last=True), None, None, None, None
+
+
+def bilinear_gather(grid, coord, scale, out=None, point_major=False):
+    """grid [B,C,H,W] (any strides), coord [B,N,K(,1)] -> out [B,C,N] (a view of a [B,N,C] buffer when
+    point_major).  Differentiable in ``grid`` (``bilinear_gather_backward``); with ``out=`` the returned tensor shares
+    ``out``'s memory and is the one that carries the graph.  There is no gradient with respect to ``coord``."""
+    grad_mode = torch.is_grad_enabled()
+    if grad_mode and coord.requires_grad:
+        raise RuntimeError("bilinear_gather: no gradient with respect to coord (the coordinates are data); detach it")
+    _require_cuda("bilinear_gather", grid, coord, out)
+    if grid.dtype != torch.float32 or coord.dtype != torch.float32:
+        raise RuntimeError("bilinear_gather: float32 only (got %s, %s)" % (grid.dtype, coord.dtype))
+    if grad_mode and grid.requires_grad:
+        return _BilinearGather.apply(grid, coord, scale, (out,), point_major)
+    return _bilinear_gather_fwd(grid, coord, scale, out, point_major)
 
 
 def msda_fwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight):

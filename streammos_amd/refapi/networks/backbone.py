@@ -4,6 +4,8 @@ Only the blocks reachable from the shipped configuration are provided (SURVEY.md
 Sub-module names and registration order reproduce the reference's ``state_dict`` keys exactly, which
 is what makes the 474-tensor checkpoint loadable with ``strict=True``; cited per class.
 """
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -126,12 +128,17 @@ class CatFusion(nn.Module):
         return self.merge_layer(x)
 
 
+_OWN_BACKWARD = os.environ.get("SMOS_BILINEAR_BWD", "1") != "0"    # A/B switch: 0 = training through F.grid_sample
+
+
 class BilinearSample(nn.Module):
     """Grid -> point bilinear gather, parameter-free -- networks/backbone.py:453-475.
 
-    grid_feat (BS, C, H, W), grid_coord (BS, N, 2, S) -> (BS, C, N, S).  GPU tensors that do not need
-    gradients use the HIP gather; anything else (CPU tensors, training) goes through ``F.grid_sample``
-    with the reference's exact formulation.
+    grid_feat (BS, C, H, W), grid_coord (BS, N, 2, S) -> (BS, C, N, S).  GPU float32 tensors with S = 1 use the HIP
+    gather: directly when nothing needs a gradient, and through its autograd node (``ops.bilinear_gather``, backward
+    kernel ``smos_bilinear_gather_bwd``) when ``grid_feat`` does.  Anything else -- CPU tensors, other dtypes, a
+    ``grid_coord`` that requires a gradient, or ``SMOS_BILINEAR_BWD=0`` for a ``grid_feat`` that does -- goes through
+    ``F.grid_sample`` with the reference's exact formulation.
     """
 
     def __init__(self, in_dim, scale_rate):
@@ -139,8 +146,10 @@ class BilinearSample(nn.Module):
         self.scale_rate = scale_rate
 
     def forward(self, grid_feat, grid_coord):
-        needs_grad = torch.is_grad_enabled() and (grid_feat.requires_grad or grid_coord.requires_grad)
-        if grid_feat.is_cuda and not needs_grad and grid_coord.shape[-1] == 1 and grid_feat.dtype == torch.float32:
+        grad_mode = torch.is_grad_enabled()
+        coord_grad = grad_mode and grid_coord.requires_grad
+        own = not coord_grad and (_OWN_BACKWARD or not (grad_mode and grid_feat.requires_grad))
+        if grid_feat.is_cuda and own and grid_coord.shape[-1] == 1 and grid_feat.dtype == torch.float32:
             return ops.bilinear_gather(grid_feat, grid_coord.float(), self.scale_rate).unsqueeze(-1)
         h, w = grid_feat.shape[2], grid_feat.shape[3]
         gx = (2 * grid_coord[:, :, 1] * self.scale_rate[1] / (w - 1)) - 1
