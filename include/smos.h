@@ -40,8 +40,8 @@ typedef void* smos_stream_t; /* hipStream_t */
 int smos_abi_version(void);
 const char* smos_last_error(void);
 /* Test hook (process-wide, not part of the data path; the one piece of state the library keeps): caps the grid of the
- * persistent convolution kernels (smos_conv_cl / _rows_cl / _wino_cl / _wino1d_cl / _bf16_cl), of smos_stem_gemm and of
- * smos_pointnet_scatter / _rows / _rows_live at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
+ * persistent convolution kernels (smos_conv_cl / _rows_cl / _wino_cl / _wino1d_cl / _bf16_cl), of smos_stem_gemm, of
+ * smos_pointnet_scatter / _rows / _rows_live and of smos_gather_scatter_cl / _live / _view at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
  * item-boundary code paths, a wave's whole-tile / head / tail units of the stem, the scatter's software pipeline -- on shapes
  * small enough to check against float64.  The results do not depend on it. */
 int smos_debug_set_conv_grid_cap(int32_t blocks);

@@ -688,7 +688,8 @@ extern "C" int smos_gather_scatter_cl_view(const float* grid, int64_t grid_pitch
   if (vec) {
     const int64_t runs = B * ((N + 63) / 64);
     const int64_t blocks = (runs + 3) / 4;
-    dim3 g((unsigned)(blocks < 256 * 32 ? blocks : 256 * 32));
+    const int64_t cap = conv_grid_cap(256 * 32);      // (the test hook's cap: several runs per wave)
+    dim3 g((unsigned)(blocks < cap ? blocks : cap));
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = out ? (size_t)4 * 64 * C * sizeof(float) : 0;       // one [64 points][C] tile per wave
     KernelSetup ks;
@@ -707,7 +708,8 @@ extern "C" int smos_gather_scatter_cl_view(const float* grid, int64_t grid_pitch
   }
   const int64_t runs = B * ((N + C - 1) / C);
   const int64_t blocks = (runs * C + kBlock - 1) / kBlock;
-  dim3 g((unsigned)(blocks < 256 * 32 ? blocks : 256 * 32));
+  const int64_t cap = conv_grid_cap(256 * 32);
+  dim3 g((unsigned)(blocks < cap ? blocks : cap));
   if (C == 32)
     hipLaunchKernelGGL((gather_scatter_cl<32>), g, dim3(kBlock), 0, (hipStream_t)stream, a);
   else

@@ -1906,7 +1906,9 @@ def gather_scatter_cl(grid, gcoord, gscale, scoord=None, sscale=None, out=None, 
     """grid: channels-last [B,C,Hg,Wg] view; out: channels-last [B,C,Ho,Wo] view, zero-filled (or None);
     pts_out: [B,N,C] rows (or None).  gcoord / scoord: [B,N,K>=2] float32 views with a dense last dimension (strided slices of
     the reference's coordinate tensors are taken as they lie).  n_live (device int32 tensor, optional): real points at the front
-    of every sample; point rows of the padding tail are not written."""
+    of every sample; point rows of the padding tail are not written.  The scatter is max(0, .) into the zero-filled target -- a
+    cell whose members are all negative stays 0, where VoxelMaxPool keeps the true maximum -- and is meant for the engine's
+    non-negative maps; the point rows carry the signed gathered values."""
     _require_cuda("gather_scatter_cl", grid, gcoord, scoord, out, pts_out, n_live)
     if n_live is not None and (n_live.dtype != torch.int32 or n_live.numel() < 1):
         raise RuntimeError("gather_scatter_cl: n_live must be a device int32 tensor")
