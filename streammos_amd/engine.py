@@ -32,7 +32,8 @@ RELU, LEAKY, NONE = ops.ACT_RELU, ops.ACT_LEAKY, ops.ACT_NONE
 
 def _fold(conv_w, conv_b, bn, pre=None):
     """(w', b') with BatchNorm `bn` (eval statistics) applied AFTER the conv and, optionally, a BatchNorm
-    `pre` applied BEFORE it (PointNet's input BN, networks/backbone.py:205-210)."""
+    `pre` applied BEFORE it (PointNet's input BN, networks/backbone.py:205-210).  w' is channels-last, the memory format of
+    the maps (for a 1x1 kernel that is the plain contiguous tensor)."""
     w = conv_w.detach().double()
     b = conv_b.detach().double() if conv_b is not None else torch.zeros(w.shape[0], dtype=torch.float64, device=w.device)
     if pre is not None:
@@ -44,19 +45,176 @@ def _fold(conv_w, conv_b, bn, pre=None):
         s = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
         w = w * s[:, None, None, None]
         b = (b - bn.running_mean.detach().double()) * s + bn.bias.detach().double()
-    return w.float().contiguous(), b.float().contiguous()
+    return w.float().contiguous(memory_format=torch.channels_last), b.float().contiguous()
 
 
-class _Obj:
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+def _block_call(eng):
+    """The switches every block call depends on, read per call: a block's two or three launches behind ONE foreign call
+    (csrc/blocks.hip; same launches, same arguments).  Profiled runs go launch by launch so that every launch keeps its label."""
+    return eng.block_call and eng.own_conv and eng.wino and not profiling.enabled()
 
 
-def _cl_w(w):
-    return w.contiguous(memory_format=torch.channels_last)
+class DownBlock:
+    """DownSample2D (networks/backbone.py): conv3x3 (stride) + BN next to conv1x1 + BN + maxpool3x3 (stride), + , ReLU."""
+    kind = "down"
+    __slots__ = ("wa", "wp", "bias", "stride", "pool_ok", "pool_pack")
+
+    def __init__(self, m):
+        self.wa, ba = _fold(m.conv_branch[0].weight, None, m.conv_branch[1])
+        self.wp, bp = _fold(m.pool_branch[0].weight, None, m.pool_branch[1])
+        # maxpool(y + b) == maxpool(y) + b for a per-channel constant b: both biases move behind the pool
+        self.bias = (ba + bp).contiguous()
+        self.stride = m.conv_branch[0].stride[0]
+        cout, cin = self.wp.shape[0], self.wp.shape[1]
+        # the 1x1 pool-branch conv, the 3x3 max pool and the tail in one launch (csrc/downsample.hip): the full-resolution
+        # branch map is never written.  Measured (tools/ubench_pool.py): 64 ch @256^2 /2 0.044 vs 0.047 ms for the two
+        # launches, 32 ch @32x1024 /1 0.019 vs 0.023, 64 ch @16x512 /1 0.014 vs 0.020 -- and 128 ch @128^2 /2 0.043 vs
+        # 0.037: the 1x1 conv is not as HBM-bound as it looks (2.1 GFLOP x 1.29 halo recompute = 19 us at the matrix
+        # peak), so the 128-channel block keeps the two launches
+        self.pool_ok = cin <= 64 and ops.pool_branch_ok(cin, cout, self.stride)
+        self.pool_pack = None           # ops.pool_branch_prepare(wp), made by the first call that takes the fused launch
+
+    def run(self, eng, x, out=None):
+        a = eng._conv(x, self.wa, None, NONE, stride=self.stride)
+        if (self.pool_ok and eng.pool_fused and eng.own_conv and
+                x.shape[0] * x.shape[2] * x.shape[3] * x.stride(3) * 4 < (1 << 31)):
+            if self.pool_pack is None:
+                self.pool_pack = ops.pool_branch_prepare(self.wp)
+            return ops.downsample_pool_branch(x, self.pool_pack, a, self.bias, self.stride, out=out if out is not None else a)
+        q = eng._conv(x, self.wp, None, NONE)
+        return ops.downsample_epilogue_cl(a, q, self.bias, self.stride, out=out if out is not None else a)
+
+
+class UnbalanceBlock:
+    """Unbalance_BasicBlock (networks/multi_view_encoder.py:478-497): conv k x 3 and conv 3 x k side by side, conv3x3 over
+    both, + x, ReLU."""
+    kind = "unbalance"
+    __slots__ = ("wa", "ba", "pa", "wb", "bb", "pb", "wc", "bc", "plan_ok", "plan")
+
+    def __init__(self, m):
+        self.wa, self.ba = _fold(m.layer7x3[0].weight, None, m.layer7x3[1])
+        self.wb, self.bb = _fold(m.layer3x7[0].weight, None, m.layer3x7[1])
+        self.wc, self.bc = _fold(m.layer3x3[0].weight, None, m.layer3x3[1])
+        self.pa, self.pb = m.layer7x3[0].padding, m.layer3x7[0].padding
+        c = self.wa.shape[0]
+        self.plan_ok = (c % 16 == 0 and tuple(self.wa.shape[:2]) == (c, c) and tuple(self.wb.shape[:2]) == (c, c) and
+                        tuple(self.wc.shape) == (c, 2 * c, 3, 3) and ops.conv_wino1d_ok(tuple(self.wa.shape[2:]), 1, c, c) and
+                        ops.conv_wino1d_ok(tuple(self.wb.shape[2:]), 1, c, c))
+        self.plan = None                # ops.UnbalanceBlockPlan, made by the first block call (a bf16 engine makes none)
+
+    def run(self, eng, x, out=None):
+        if self.plan_ok and _block_call(eng) and eng.wino1d and 2 * x.numel() <= (1 << 26):
+            if self.plan is None:
+                self.plan = ops.UnbalanceBlockPlan(self.wa, self.ba, self.wb, self.bb, self.wc, self.bc)
+            return ops.unbalance_block_cl(x, self.plan, out=out)
+        b, c, h, w = x.shape
+        both = ops.empty_cl(b, 2 * c, h, w, x.device)
+        eng._conv(x, self.wa, self.ba, RELU, out=both[:, :c])
+        eng._conv(x, self.wb, self.bb, RELU, out=both[:, c:])
+        return eng._conv(both, self.wc, self.bc, RELU, residual=x, out=out)
+
+
+class BasicBlock:
+    """BasicBlock (networks/backbone.py:136-159): conv3x3 + BN + ReLU, conv3x3 + BN [, ChannelAtt gate], + x, ReLU."""
+    kind = "basic"
+    __slots__ = ("w1", "b1", "w2", "b2", "att", "cw1", "cb1", "cw2", "cb2", "plan_ok", "plan", "scratch")
+
+    def __init__(self, m):
+        self.w1, self.b1 = _fold(m.layer[0].weight, None, m.layer[1])
+        self.w2, self.b2 = _fold(m.layer[3].weight, None, m.layer[4])
+        self.att = m.use_att
+        self.cw1 = self.cb1 = self.cw2 = self.cb2 = None            # the gate MLP of a ChannelAtt block
+        if m.use_att:
+            c1, c2 = m.channel_att.cnet[1], m.channel_att.cnet[3]
+            self.cw1 = c1.weight.detach().reshape(c1.weight.shape[0], -1).contiguous()
+            self.cb1 = c1.bias.detach().contiguous()
+            self.cw2 = c2.weight.detach().reshape(c2.weight.shape[0], -1).contiguous()
+            self.cb2 = c2.bias.detach().contiguous()
+        c = self.w1.shape[0]
+        self.plan_ok = tuple(self.w1.shape) == (c, c, 3, 3) and tuple(self.w2.shape) == (c, c, 3, 3) and ops.basic_block_ok(c, self.att)
+        self.plan = None                # ops.BasicBlockPlan, made by the first block call (a bf16 engine makes none)
+        self.scratch = None             # gated blocks: {(stream, namespace): plane sums}, see InferenceEngine._block_ws
+
+    def run(self, eng, x, out=None):
+        # a gated block call takes its pool sums from the conv epilogue: without fused_gate_sums it goes launch by launch
+        if (self.plan_ok and _block_call(eng) and (eng.fused_gate_sums or not self.att) and x.numel() <= (1 << 26)):
+            if self.plan is None:
+                self.plan = ops.BasicBlockPlan(self.w1, self.b1, self.w2, self.b2,
+                                               (self.cw1, self.cb1, self.cw2, self.cb2) if self.att else None)
+            ws = None
+            if self.att:
+                bsz, c, h, w = x.shape
+                ws = eng._block_ws(self, bsz * c * (ops.conv_wino_sum_chunks(h, w) + 1))
+            return ops.basic_block_cl(x, self.plan, out=out, ws=ws)
+        y = eng._conv(x, self.w1, self.b1, RELU)
+        if not self.att:
+            return eng._conv(y, self.w2, self.b2, RELU, residual=x, out=out)
+        bsz, c, h, w = y.shape
+        k2 = tuple(self.w2.shape[2:])
+        if (eng.own_conv and eng.fused_gate_sums and ops.gate_channels_ok(c) and ops.conv_cl_supported(y, c, k2) and
+                (not eng._bf16 or ops.conv_bf16_ok(y, c, k2, chan_sums=True))):
+            # the conv's epilogue leaves the per-row-segment channel sums behind: no pass over y2 for the average pool
+            # (bf16 mode: the bf16 kernel writes them, in the table layout of conv_cl)
+            # the table's layout is the kernel's, so the function that picks the kernel in _conv picks it here
+            family = "bf16" if eng._bf16 else ops.conv_route(c, c, k2, 1, bsz * h * w, False, True, eng)[0]
+            chunks = ops.conv_wino_sum_chunks(h, w) if family == "wino" else ops.conv_sum_chunks(h, w)
+            ws = eng._block_ws(self, bsz * c * (chunks + 1))
+            sums = ws[:bsz * chunks * c].view(bsz, chunks, c)
+            y2 = eng._conv(y, self.w2, None, NONE, chan_sums=sums)
+            return ops.channel_gate_apply_cl(y2, self.b2, self.cw1, self.cb1, self.cw2, self.cb2, x, sums, ws[bsz * chunks * c:],
+                                             out=out if out is not None else y2)
+        y2 = eng._conv(y, self.w2, None, NONE)
+        need = (y2.shape[2] * y2.shape[3] // 512 + 2) * y2.shape[0] * y2.shape[1]
+        return ops.channel_gate_residual_cl(y2, self.b2, self.cw1, self.cb1, self.cw2, self.cb2, x, eng._block_ws(self, need),
+                                            out=out if out is not None else y2)
+
+
+class FusionLayer:
+    """One DeformAttnLayer of the temporal fusion (multi_view_encoder.py:245-321): its weights as (W, b) pairs, and what the
+    own kernels stream (tf, wv_stream, wq_stream: filled in by InferenceEngine.__init__ where csrc/tfusion.hip covers the layer)."""
+    __slots__ = ("heads", "points", "value", "qproj", "out", "norm1", "lin1", "lin2", "norm2", "tf", "wv_stream", "wq_stream")
+
+    def __init__(self, lyr):
+        ca = lyr.cross_attn
+        self.heads, self.points = ca.n_heads, ca.n_points
+        self.value = (ca.value_proj.weight.detach(), ca.value_proj.bias.detach())
+        # one GEMM for offsets and attention logits
+        self.qproj = (torch.cat((ca.sampling_offsets.weight.detach(), ca.attention_weights.weight.detach()), 0).contiguous(),
+                      torch.cat((ca.sampling_offsets.bias.detach(), ca.attention_weights.bias.detach()), 0).contiguous())
+        self.out = (ca.output_proj.weight.detach(), ca.output_proj.bias.detach())
+        self.norm1 = (lyr.norm1.weight.detach(), lyr.norm1.bias.detach(), lyr.norm1.eps)
+        self.lin1 = (lyr.linear1.weight.detach(), lyr.linear1.bias.detach())
+        self.lin2 = (lyr.linear2.weight.detach(), lyr.linear2.bias.detach())
+        self.norm2 = (lyr.norm2.weight.detach(), lyr.norm2.bias.detach(), lyr.norm2.eps)
+        self.tf = self.wv_stream = self.wq_stream = None
 
 
 CONV_PRECISIONS = ("fp32", "bf16")
+
+# The A/B switches: (attribute, environment variable, default, kind); kind "bool" parses as != "0", "int" as int().  Each is a
+# plain attribute read on every call, so setting one on a live engine selects the other route from the next call on.
+SWITCHES = (
+    ("sparse_stem", "SMOS_SPARSE_STEM", True, "bool"),        # first BEV stage on the occupied cells (AttNet.engine_sparse_stem overrides)
+    # temporal fusion on the own MFMA kernels (csrc/tfusion.hip): value_proj of every layer + the first layer's offset /
+    # logit projection as ONE launch, then per layer the sampler and ONE kernel for output_proj -> +query -> LayerNorm ->
+    # FFN -> + -> LayerNorm (-> the next layer's projection).  0: the library-GEMM form
+    ("tfusion", "SMOS_TFUSION", True, "bool"),
+    # conv_1 without the upsampled concatenation (csrc/upconv.hip): direct conv on the fine map's channels, tap GEMMs
+    # at source resolution for the two coarser maps; the aux heads likewise run before the (linear) upsampling
+    ("upconv", "SMOS_UPCONV", True, "bool"),
+    ("fused_head", "SMOS_FUSED_HEAD", True, "bool"),          # fused point head (csrc/point_head.hip) for the 192 -> 96 -> 64 -> 3 head
+    ("head_gather", "SMOS_HEAD_GATHER", True, "bool"),        # the fused head gathers the decoder's BEV rows itself: no gather launch
+    # every 2-D convolution runs on the library's own kernels with the epilogue fused.  0: MIOpen convs + separate
+    # epilogue passes (kept for A/B runs; tools/ubench_conv.py compares the two per layer)
+    ("own_conv", "SMOS_OWN_CONV", True, "bool"),
+    ("conv_rows_mt", "SMOS_CONV_ROWS_MT", 1, "int"),          # largest mt the row-staging conv is used for
+    ("conv_rows", "SMOS_CONV_ROWS", 3, "int"),                # n > 0: row-staging conv for KW >= n at mt = 1; 0: off
+    ("fused_gate_sums", "SMOS_GATE_SUMS", True, "bool"),      # ChannelAtt pool sums from the conv epilogue
+    ("wino", "SMOS_WINO", True, "bool"),                      # Winograd F(2x2,3x3) for the stride-1 3x3 layers
+    ("wino1d", "SMOS_WINO1D", True, "bool"),                  # 1-D Winograd F(2,3) for the k x 3 / 3 x k layers
+    ("pool_fused", "SMOS_POOL_FUSED", True, "bool"),          # DownSample2D pool branch + tail in one launch
+    ("block_call", "SMOS_BLOCK_CALL", True, "bool"),          # a residual block = one foreign call (same launches)
+)
 
 
 class InferenceEngine:
@@ -76,6 +234,12 @@ class InferenceEngine:
         self._bf16 = conv_precision == "bf16"
         self._conv_layers = {}          # id(folded weight) -> ops.ConvLayer (which holds the weight): see _conv
         self.device = next(net.parameters()).device
+        for attr, var, default, kind in SWITCHES:
+            v = os.environ.get(var)
+            setattr(self, attr, default if v is None else (v != "0" if kind == "bool" else int(v)))
+        if self._bf16:
+            # the block calls launch fp32 kernels: bf16 mode takes the launch-by-launch path
+            self.block_call = False
         self.bev_hw = tuple(net.bev_wl_shape)
         enc = net.bev_net
 
@@ -86,7 +250,6 @@ class InferenceEngine:
         self.header_bev = [self._block(m) for m in enc.header_bev]
         # sparse first stage (csrc/stem.hip): per parity class of the input cell, the kernel taps that can reach an
         # output pixel under stride 2, stacked with the 1x1 pool-branch weights, in MFMA operand order
-        self.sparse_stem = os.environ.get("SMOS_SPARSE_STEM", "1") != "0"     # A/B switch (AttNet.engine_sparse_stem overrides)
         self.stem_w = None
         p0 = self.header_bev[0]
         if (p0.kind == "down" and p0.stride == 2 and p0.wa.shape[0] == 32 and p0.wa.shape[1] == 192 and
@@ -98,25 +261,9 @@ class InferenceEngine:
         self.res2 = [self._block(m) for m in enc.res2]
 
         self.query_embed = enc.query_embed.weight.detach()
-        self.layers = []
-        for lyr in enc.deformattn_module.deformattn_layers:
-            ca = lyr.cross_attn
-            self.layers.append(_Obj(
-                heads=ca.n_heads, points=ca.n_points,
-                value=(ca.value_proj.weight.detach(), ca.value_proj.bias.detach()),
-                # one GEMM for offsets and attention logits
-                qproj=(torch.cat((ca.sampling_offsets.weight.detach(), ca.attention_weights.weight.detach()), 0).contiguous(),
-                       torch.cat((ca.sampling_offsets.bias.detach(), ca.attention_weights.bias.detach()), 0).contiguous()),
-                out=(ca.output_proj.weight.detach(), ca.output_proj.bias.detach()),
-                norm1=(lyr.norm1.weight.detach(), lyr.norm1.bias.detach(), lyr.norm1.eps),
-                lin1=(lyr.linear1.weight.detach(), lyr.linear1.bias.detach()),
-                lin2=(lyr.linear2.weight.detach(), lyr.linear2.bias.detach()),
-                norm2=(lyr.norm2.weight.detach(), lyr.norm2.bias.detach(), lyr.norm2.eps)))
+        self.layers = [FusionLayer(lyr) for lyr in enc.deformattn_module.deformattn_layers]
 
-        # temporal fusion on the own MFMA kernels (csrc/tfusion.hip): value_proj of every layer + the first layer's offset /
-        # logit projection as ONE launch, then per layer the sampler and ONE kernel for output_proj -> +query -> LayerNorm ->
-        # FFN -> + -> LayerNorm (-> the next layer's projection).  SMOS_TFUSION=0: the library-GEMM form (A/B switch).
-        self.tfusion = os.environ.get("SMOS_TFUSION", "1") != "0"
+        # what the own temporal-fusion kernels stream (the tfusion switch)
         self._tf_ok = False
         try:
             for i, L in enumerate(self.layers):
@@ -141,11 +288,9 @@ class InferenceEngine:
             off += cin[i]
         self.aux = (w.contiguous(), torch.cat([h.bias.detach() for h in heads]).contiguous(), ncls)
         self.grid2point_scale = tuple(net.bev_grid2point.scale_rate)
-        # conv_1 without the upsampled concatenation (csrc/upconv.hip): direct conv on the fine map's channels, tap GEMMs
-        # at source resolution for the two coarser maps; the aux heads likewise run before the (linear) upsampling
-        self.upconv = os.environ.get("SMOS_UPCONV", "1") != "0"
+        # the operands of the upconv switch: conv_1 cut into the fine map's channels and the two coarser maps' tap matrices
         w1 = self.conv_1[0]
-        self.conv_1a = w1[:, :cin[0]].contiguous()
+        self.conv_1a = w1[:, :cin[0]].contiguous(memory_format=torch.channels_last)
         self.conv_1z = (ops.upconv_tap_weights(w1, cin[0], cin[0] + cin[1]), ops.upconv_tap_weights(w1, cin[0] + cin[1], sum(cin)))
         self.aux_split = [(h.weight.detach().contiguous(), h.bias.detach().contiguous()) for h in heads]
 
@@ -160,10 +305,7 @@ class InferenceEngine:
             rp = net.refine.bf_pred_layer.pred_layer[0]
             self.refine = (_fold(rm[0].weight, None, rm[1]), _fold(rm[3].weight, None, rm[4]),
                            (rp.weight.detach().contiguous(), rp.bias.detach().contiguous()))
-        # fused point head (csrc/point_head.hip) when the head has the reference's 192 -> 96 -> 64 -> 3 shape
-        self.fused_head = os.environ.get("SMOS_FUSED_HEAD", "1") != "0"
-        # the fused head gathers the decoder's BEV rows itself instead of reading them back from a gather launch (A/B switch)
-        self.head_gather = os.environ.get("SMOS_HEAD_GATHER", "1") != "0"
+        # the fused point head's operands, where the head has the reference's 192 -> 96 -> 64 -> 3 shape
         self.head_w = self.refine_w = None
         try:
             self.head_w = ops.point_head_prepare(self.post1, self.post2, self.pred)
@@ -171,31 +313,6 @@ class InferenceEngine:
                 self.refine_w = ops.point_head_prepare(*self.refine)
         except RuntimeError:
             self.head_w = self.refine_w = None
-        # the folded weights in the memory format of the maps
-        for blocks in (self.header_bev, self.header_rv, self.res1_bev, self.res1_rv, self.res2):
-            for p in blocks:
-                for k in ("wa", "wp", "wb", "wc", "w1", "w2"):
-                    if hasattr(p, k):
-                        setattr(p, k, _cl_w(getattr(p, k)))
-        self.conv_1a = _cl_w(self.conv_1a)
-        self.aux_split = [(_cl_w(w), b) for w, b in self.aux_split]
-        self.conv_1 = (_cl_w(self.conv_1[0]), self.conv_1[1])
-        self.conv_2 = (_cl_w(self.conv_2[0]), self.conv_2[1])
-        self.aux = (_cl_w(self.aux[0]), self.aux[1], self.aux[2])
-        # every 2-D convolution of the channels-last engine runs on the library's own implicit-GEMM kernel with the
-        # epilogue fused (csrc/conv_igemm.hip).  SMOS_OWN_CONV=0 falls back to MIOpen convs + separate epilogue passes
-        # (kept for A/B runs; tools/ubench_conv.py compares the two per layer).
-        self.own_conv = os.environ.get("SMOS_OWN_CONV", "1") != "0"
-        self.conv_rows_mt = int(os.environ.get("SMOS_CONV_ROWS_MT", "1"))      # largest mt the row-staging conv is used for
-        self.conv_rows = int(os.environ.get("SMOS_CONV_ROWS", "3"))      # n > 0: row-staging conv for KW >= n at mt = 1; 0: off
-        self.fused_gate_sums = os.environ.get("SMOS_GATE_SUMS", "1") != "0"      # ChannelAtt pool sums from the conv epilogue
-        self.wino = os.environ.get("SMOS_WINO", "1") != "0"      # Winograd F(2x2,3x3) for the stride-1 3x3 layers (A/B switch)
-        self.wino1d = os.environ.get("SMOS_WINO1D", "1") != "0"  # 1-D Winograd F(2,3) for the k x 3 / 3 x k layers (A/B switch)
-        self.pool_fused = os.environ.get("SMOS_POOL_FUSED", "1") != "0"   # DownSample2D pool branch + tail in one launch (A/B switch)
-        self.block_call = os.environ.get("SMOS_BLOCK_CALL", "1") != "0"   # BasicBlock = one foreign call (A/B switch; same launches)
-        if self._bf16:
-            # the block calls launch fp32 kernels: bf16 mode takes the launch-by-launch path
-            self.block_call = False
         self._shapes = None
         self._lsi = None
         self._hw = None
@@ -205,28 +322,9 @@ class InferenceEngine:
     def _block(self, m):
         from .refapi.networks import backbone as bb
         from .refapi.networks import multi_view_encoder as mve
-        if isinstance(m, bb.DownSample2D):
-            wa, ba = _fold(m.conv_branch[0].weight, None, m.conv_branch[1])
-            wp, bp = _fold(m.pool_branch[0].weight, None, m.pool_branch[1])
-            # maxpool(y + b) == maxpool(y) + b for a per-channel constant b: both biases move behind the pool
-            return _Obj(kind="down", wa=wa, wp=wp, bias=(ba + bp).contiguous(), stride=m.conv_branch[0].stride[0])
-        if isinstance(m, mve.Unbalance_BasicBlock):
-            wa, ba = _fold(m.layer7x3[0].weight, None, m.layer7x3[1])
-            wb, bb_ = _fold(m.layer3x7[0].weight, None, m.layer3x7[1])
-            wc, bc = _fold(m.layer3x3[0].weight, None, m.layer3x3[1])
-            return _Obj(kind="unbalance", wa=wa, ba=ba, pa=m.layer7x3[0].padding, wb=wb, bb=bb_, pb=m.layer3x7[0].padding,
-                        wc=wc, bc=bc)
-        if isinstance(m, bb.BasicBlock):
-            w1, b1 = _fold(m.layer[0].weight, None, m.layer[1])
-            w2, b2 = _fold(m.layer[3].weight, None, m.layer[4])
-            o = _Obj(kind="basic", w1=w1, b1=b1, w2=w2, b2=b2, att=m.use_att)
-            if m.use_att:
-                c1, c2 = m.channel_att.cnet[1], m.channel_att.cnet[3]
-                o.cw1 = c1.weight.detach().reshape(c1.weight.shape[0], -1).contiguous()
-                o.cb1 = c1.bias.detach().contiguous()
-                o.cw2 = c2.weight.detach().reshape(c2.weight.shape[0], -1).contiguous()
-                o.cb2 = c2.bias.detach().contiguous()
-            return o
+        for cls, module in ((DownBlock, bb.DownSample2D), (UnbalanceBlock, mve.Unbalance_BasicBlock), (BasicBlock, bb.BasicBlock)):
+            if isinstance(m, module):
+                return cls(m)
         raise RuntimeError("InferenceEngine: unexpected module %s" % type(m).__name__)
 
     # ---- blocks ---------------------------------------------------------------------------
@@ -276,9 +374,9 @@ class InferenceEngine:
         hipGraphs captured from one engine for several TTA groups replay concurrently with the addresses baked in
         (namespace = group index, ops.set_workspace_namespace in StreamRunner._capture) -- a shared scratch would be a data
         race in each case."""
-        table = p.__dict__.get("ws")
+        table = p.scratch
         if table is None:
-            table = p.__dict__["ws"] = ops.new_block_scratch(self.device)     # registered: release_stream_workspaces purges it
+            table = p.scratch = ops.new_block_scratch(self.device)     # registered: release_stream_workspaces purges it
         key = (ops._raw_stream(ops._dev_index(self.device)), ops._ws_namespace)
         ws = table.get(key)
         if ws is None or ws.numel() < n_floats:
@@ -437,77 +535,11 @@ class InferenceEngine:
         return ops.conv_cl(x, wp, bias, act, cout, (kh, kw), stride=stride, mt=tile, residual=residual, out=out, chan_sums=chan_sums)
 
     def _block_cl(self, x, p, out=None):
-        if p.kind == "down":
-            a = self._conv(x, p.wa, None, NONE, stride=p.stride)
-            cout, cin = p.wp.shape[0], p.wp.shape[1]
-            if (self.pool_fused and self.own_conv and cin <= 64 and ops.pool_branch_ok(cin, cout, p.stride) and
-                    x.shape[0] * x.shape[2] * x.shape[3] * x.stride(3) * 4 < (1 << 31)):
-                # the 1x1 pool-branch conv, the 3x3 max pool and the tail in one launch (csrc/downsample.hip): the full-resolution
-                # branch map is never written.  Measured (tools/ubench_pool.py): 64 ch @256^2 /2 0.044 vs 0.047 ms for the two
-                # launches, 32 ch @32x1024 /1 0.019 vs 0.023, 64 ch @16x512 /1 0.014 vs 0.020 -- and 128 ch @128^2 /2 0.043 vs
-                # 0.037: the 1x1 conv is not as HBM-bound as it looks (2.1 GFLOP x 1.29 halo recompute = 19 us at the matrix
-                # peak), so the 128-channel block keeps the two launches
-                wq = p.__dict__.get("wq")
-                if wq is None:
-                    wq = p.__dict__["wq"] = ops.pool_branch_prepare(p.wp)
-                return ops.downsample_pool_branch(x, wq, a, p.bias, p.stride, out=out if out is not None else a)
-            q = self._conv(x, p.wp, None, NONE)
-            return ops.downsample_epilogue_cl(a, q, p.bias, p.stride, out=out if out is not None else a)
-        if p.kind == "unbalance":
-            b, c, h, w = x.shape
-            if self.block_call and self.own_conv and self.wino and self.wino1d and not profiling.enabled():
-                plan = p.__dict__.get("plan")
-                if plan is None:
-                    ok = (c % 16 == 0 and tuple(p.wc.shape) == (c, 2 * c, 3, 3) and
-                          ops.conv_wino1d_ok(tuple(p.wa.shape[2:]), 1, c, c) and ops.conv_wino1d_ok(tuple(p.wb.shape[2:]), 1, c, c))
-                    plan = p.__dict__["plan"] = ops.UnbalanceBlockPlan(p.wa, p.ba, p.wb, p.bb, p.wc, p.bc) if ok else False
-                if plan and 2 * x.numel() <= (1 << 26):
-                    return ops.unbalance_block_cl(x, plan, out=out)
-            both = ops.empty_cl(b, 2 * c, h, w, x.device)
-            self._conv(x, p.wa, p.ba, RELU, out=both[:, :c])
-            self._conv(x, p.wb, p.bb, RELU, out=both[:, c:])
-            return self._conv(both, p.wc, p.bc, RELU, residual=x, out=out)
-        if self.block_call and self.own_conv and self.wino and not profiling.enabled():
-            # the block's two or three launches behind ONE foreign call (csrc/blocks.hip; same launches, same arguments).
-            # Profiled runs take the launch-by-launch path below so that every launch keeps its label.
-            plan = p.__dict__.get("plan")
-            if plan is None:
-                c = p.w1.shape[0]
-                ok = (tuple(p.w1.shape) == (c, c, 3, 3) and tuple(p.w2.shape) == (c, c, 3, 3) and ops.basic_block_ok(c, p.att) and
-                      (not p.att or self.fused_gate_sums))
-                plan = p.__dict__["plan"] = ops.BasicBlockPlan(p.w1, p.b1, p.w2, p.b2,
-                                                               (p.cw1, p.cb1, p.cw2, p.cb2) if p.att else None) if ok else False
-            if plan and x.numel() <= (1 << 26):
-                ws = None
-                if p.att:
-                    bsz, c, h, w = x.shape
-                    ws = self._block_ws(p, bsz * c * (ops.conv_wino_sum_chunks(h, w) + 1))
-                return ops.basic_block_cl(x, plan, out=out, ws=ws)
-        y = self._conv(x, p.w1, p.b1, RELU)
-        if not p.att:
-            return self._conv(y, p.w2, p.b2, RELU, residual=x, out=out)
-        bsz, c, h, w = y.shape
-        if (self.own_conv and self.fused_gate_sums and c % 32 == 0 and c <= 256 and 1024 % c == 0 and
-                ops.conv_cl_supported(y, c, tuple(p.w2.shape[2:])) and
-                (not self._bf16 or ops.conv_bf16_ok(y, c, tuple(p.w2.shape[2:]), chan_sums=True))):
-            # the conv's epilogue leaves the per-row-segment channel sums behind: no pass over y2 for the average pool
-            # (bf16 mode: the bf16 kernel writes them, in the table layout of conv_cl)
-            # the table's layout is the kernel's, so the function that picks the kernel in _conv picks it here
-            family = "bf16" if self._bf16 else ops.conv_route(c, c, tuple(p.w2.shape[2:]), 1, bsz * h * w, False, True, self)[0]
-            chunks = ops.conv_wino_sum_chunks(h, w) if family == "wino" else ops.conv_sum_chunks(h, w)
-            ws = self._block_ws(p, bsz * c * (chunks + 1))
-            sums = ws[:bsz * chunks * c].view(bsz, chunks, c)
-            y2 = self._conv(y, p.w2, None, NONE, chan_sums=sums)
-            return ops.channel_gate_apply_cl(y2, p.b2, p.cw1, p.cb1, p.cw2, p.cb2, x, sums, ws[bsz * chunks * c:],
-                                             out=out if out is not None else y2)
-        y2 = self._conv(y, p.w2, None, NONE)
-        need = (y2.shape[2] * y2.shape[3] // 512 + 2) * y2.shape[0] * y2.shape[1]
-        return ops.channel_gate_residual_cl(y2, p.b2, p.cw1, p.cb1, p.cw2, p.cb2, x, self._block_ws(p, need),
-                                            out=out if out is not None else y2)
+        return p.run(self, x, out)
 
     def _stage_cl(self, x, blocks, out=None):
         for i, p in enumerate(blocks):
-            x = self._block_cl(x, p, out if i == len(blocks) - 1 else None)
+            x = p.run(self, x, out if i == len(blocks) - 1 else None)
         return x
 
     def _cross_view_cl(self, cat_buf, c, bev_xy, sphere, rv_blocks, rv_hw, scale, point_rows=None, n_live=None, rv=None):

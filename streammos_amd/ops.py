@@ -1010,9 +1010,14 @@ def unbalance_block_cl(x, plan, both=None, out=None):
     return out
 
 
+def gate_channels_ok(c):
+    """Channel counts the ChannelAtt gate kernels take where the conv epilogue leaves the pool sums (channel_gate_apply_cl)."""
+    return c % 32 == 0 and c <= 256 and 1024 % c == 0
+
+
 def basic_block_ok(c, gated):
     """Channel counts smos_basic_block_cl takes in the engine (those of the gate kernel where the block has one)."""
-    return c % 16 == 0 and (not gated or (c % 32 == 0 and c <= 256 and 1024 % c == 0))
+    return c % 16 == 0 and (not gated or gate_channels_ok(c))
 
 
 def basic_block_cl(x, plan, y=None, out=None, ws=None):

@@ -1,5 +1,8 @@
 """End-to-end parity of AttNet.infer on the GPU (HIP kernels + PyTorch-ROCm convs) against the golden
 vectors of the real reference and against the CPU oracle, plus the streaming runner with voting."""
+import contextlib
+from unittest import mock
+
 import numpy as np
 import pytest
 import torch
@@ -184,13 +187,95 @@ def test_block_call_is_bit_identical(model):
             outs.append(res)
     finally:
         eng.block_call = True
-    plans = [p.__dict__.get("plan") for p in eng.res2 if p.kind == "basic"]
+    plans = [p.plan for p in eng.res2 if p.kind == "basic"]
     assert plans and all(plans) and any(pl.gated for pl in plans)        # the third stage did go through the block call
-    unb = [p.__dict__.get("plan") for stage in (eng.header_bev, eng.header_rv, eng.res1_bev, eng.res1_rv, eng.res2)
+    unb = [p.plan for stage in (eng.header_bev, eng.header_rv, eng.res1_bev, eng.res1_rv, eng.res2)
            for p in stage if p.kind == "unbalance"]
     assert unb and all(unb)                                              # and so did the Unbalance blocks
     for (p0, m0), (p1, m1) in zip(*outs):
         assert torch.equal(p0, p1) and torch.equal(m0, m1)
+
+
+@contextlib.contextmanager
+def _block_launches():
+    """Counts the calls of the three wrappers a residual block's routes differ in."""
+    from streammos_amd import ops
+    seen = {}
+
+    def counted(name):
+        fn = getattr(ops, name)
+        seen[name] = 0
+
+        def call(*args, **kw):
+            seen[name] += 1
+            return fn(*args, **kw)
+        return mock.patch.object(ops, name, call)
+
+    with counted("basic_block_cl"), counted("unbalance_block_cl"), counted("channel_gate_residual_cl"):
+        yield seen
+
+
+def _run_block(eng, p, x):
+    with _block_launches() as seen, torch.no_grad(), eng._conv_flags():
+        y = eng._block_cl(x, p).clone()
+    return y, (seen["basic_block_cl"], seen["unbalance_block_cl"], seen["channel_gate_residual_cl"])
+
+
+def _block_input(seed):
+    """[2, 32, 9, 33] channels-last: two samples, one row and one column past the 8 x 32 chunk of the Winograd sum table."""
+    x = torch.randn((2, 32, 9, 33), generator=torch.Generator().manual_seed(seed))
+    return x.to(DEV).contiguous(memory_format=torch.channels_last)
+
+
+def test_gated_block_follows_the_switches_per_call(model):
+    """One gated BasicBlock (C = 32, the smallest width the gate kernels take) on a live engine: the switches are read on
+    every call, so after a block call with the default switches, fused_gate_sums = False takes the same block through
+    channel_gate_residual_cl (1e-5 of the range, the bar of test_engine_variants_agree for this pair of paths), and
+    block_call = False through the separate launches of the block call (bit-identical, as test_block_call_is_bit_identical)."""
+    with torch.no_grad():
+        eng = model._engine_for(torch.zeros(1, device=DEV))
+    p = next(b for b in eng.header_bev if b.kind == "basic" and b.att)
+    assert p.w1.shape[0] == 32 and eng.block_call and eng.fused_gate_sums
+    x = _block_input(5)
+    try:
+        a, calls = _run_block(eng, p, x)
+        assert calls == (1, 0, 0) and p.plan is not None and p.plan.gated
+        eng.fused_gate_sums = False
+        b, calls = _run_block(eng, p, x)
+        assert calls == (0, 0, 1), calls
+        err = (a - b).abs().max().item() / a.abs().max().item()
+        print("gated block, pool sums from their own pass: %.2e of range" % err)
+        assert err <= 1e-5
+        eng.fused_gate_sums, eng.block_call = True, False
+        c, calls = _run_block(eng, p, x)
+        assert calls == (0, 0, 0) and torch.equal(a, c)
+    finally:
+        eng.fused_gate_sums, eng.block_call = True, True
+
+
+def test_unbalance_block_follows_the_switches_per_call(model):
+    """The same for one Unbalance block (C = 32, 7 x 3 / 3 x 7) and wino1d: off, the branches run on the direct kernels, within
+    the bar tests/test_gpu_ops.py::test_conv_wino_cl_against_float64 holds a Winograd and a direct kernel to against each other
+    (4e-6 of the range)."""
+    with torch.no_grad():
+        eng = model._engine_for(torch.zeros(1, device=DEV))
+    p = next(b for b in eng.header_bev if b.kind == "unbalance")
+    assert p.wa.shape[0] == 32 and eng.block_call and eng.wino1d
+    x = _block_input(6)
+    try:
+        a, calls = _run_block(eng, p, x)
+        assert calls == (0, 1, 0) and p.plan is not None
+        eng.wino1d = False
+        b, calls = _run_block(eng, p, x)
+        assert calls == (0, 0, 0), calls
+        err = (a - b).abs().max().item() / a.abs().max().item()
+        print("unbalance block, branches on the direct kernels: %.2e of range" % err)
+        assert err <= 4e-6
+        eng.wino1d, eng.block_call = True, False
+        c, calls = _run_block(eng, p, x)
+        assert calls == (0, 0, 0) and torch.equal(a, c)
+    finally:
+        eng.wino1d, eng.block_call = True, True
 
 
 @pytest.mark.parametrize("fill", ["lidar", "empty_sample", "dense_corner"])
