@@ -312,6 +312,7 @@ int smos_add_layer_norm(const float* x, const float* res, const float* gamma, co
  * x [B, H, W, *], res / out [B, Ho, Wo, *]: row pitches in floats (multiples of 4; channel slices of wider buffers are
  * fine), 16-byte aligned, each tensor < 2 GiB.  Cin % 32 == 0, Cout % (32 * mt) == 0, mt in {1, 2, 4} = 32-channel output
  * blocks per wave (a tuning knob), KH, KW <= 7, stride 1 or 2.  bias / res may be NULL.
+ * The window has to fit the padded image (KH <= H + 2 pad_h, KW <= W + 2 pad_w); act(NaN) is NaN, as in the reference.
  * wprep: Cout * Cin * KH * KW floats in MFMA operand order for the chosen mt; with stage = (ky * KW + kx) * (Cin / 32) + cc:
  *   wprep[((((ct * n_stage + stage) * 4 + i4) * mt + m) * 64 + lane) * 4 + c]
  *       = w[ct * 32 * mt + m * 32 + (lane & 31)][cc * 32 + 8 * i4 + 4 * (lane >> 5) + c][ky][kx].

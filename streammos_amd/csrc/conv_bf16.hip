@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16(ConvBf16Args a) {
           for (int c = 0; c < 4; ++c) {
             float v = acc[rw][mt][4 * g + c] + bb[c];
             if constexpr (RES) v += __uint_as_float(rres[(rw * MT + mt) * 4 + g][c]);
-            o[c] = __builtin_fmaf(a.slope, fminf(v, 0.f), fmaxf(v, 0.f));
+            o[c] = conv_act(v, a.slope);
             acc[rw][mt][4 * g + c] = 0.0f;
           }
           if constexpr (SUMS) {

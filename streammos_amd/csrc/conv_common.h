@@ -98,4 +98,12 @@ inline int conv_check_operands(const char* who, const void* x, int64_t x_pitch, 
 // activation code of the C ABI (0 none, 1 ReLU, 2 LeakyReLU) -> slope of max(v, 0) + slope * min(v, 0)
 inline float act_slope(int act) { return act == 0 ? 1.0f : act == 1 ? 0.0f : 0.01f; }
 
+// none / ReLU / LeakyReLU without a branch: max(v, 0) + slope * min(v, 0), slope = 1 / 0 / 0.01 (one of the two terms is
+// always zero, so this is exact).  The maximum is a select, not fmaxf: fmaxf(NaN, 0) and fminf(NaN, 0) are both 0, which
+// turned a NaN sum into a stored 0 -- the reference's ReLU / LeakyReLU hand a NaN on, and so does this (NaN <= 0 is false).
+// For every other v the select is fmaxf(v, 0): the stored bits are unchanged.
+__device__ __forceinline__ float conv_act(float v, float slope) {
+  return __builtin_fmaf(slope, fminf(v, 0.f), v <= 0.f ? 0.f : v);
+}
+
 }  // namespace smos

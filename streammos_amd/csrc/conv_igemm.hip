@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm(ConvArgs a) {
           if constexpr (RES) v += __uint_as_float(rr[4 * mt + g][c]);
           // none / ReLU / LeakyReLU without a branch: max(v, 0) + slope * min(v, 0), slope = 1 / 0 / 0.01 (one of the two
           // terms is always zero, so this is exact)
-          o[c] = __builtin_fmaf(a.slope, fminf(v, 0.f), fmaxf(v, 0.f));
+          o[c] = conv_act(v, a.slope);
           acc[mt][4 * g + c] = 0.0f;
         }
         if constexpr (SUMS) {
@@ -415,7 +415,8 @@ extern "C" int smos_conv_cl(const float* x, int64_t x_pitch, const float* wprep,
   SMOS_REQUIRE(KH >= 1 && KW >= 1 && KH <= 7 && KW <= 7 && (stride == 1 || stride == 2) && pad_h >= 0 && pad_w >= 0 &&
                    act >= 0 && act <= 2, "conv_cl: kernel up to 7 x 7, stride 1 or 2");
   const int64_t Ho = (H + 2 * pad_h - KH) / stride + 1, Wo = (W + 2 * pad_w - KW) / stride + 1;
-  SMOS_REQUIRE(Ho > 0 && Wo > 0, "conv_cl: empty output");
+  // (the window has to fit the padded image: at stride 2 the division above rounds -1 / 2 to 0, i.e. to one output row)
+  SMOS_REQUIRE(H + 2 * pad_h >= KH && W + 2 * pad_w >= KW && Ho > 0 && Wo > 0, "conv_cl: empty output");
   ConvBytes nb;
   if (int rc = conv_check_operands("conv_cl", x, x_pitch, wprep, bias, res, res_pitch, out, out_pitch, chan_sums, Cin, Cout,
                                    B * H * W, B * Ho * Wo, &nb))

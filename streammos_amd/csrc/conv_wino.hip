@@ -370,7 +370,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino(WinoArgs a) {
         u32x4 ov;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float o = __builtin_fmaf(a.slope, fminf(v[e], 0.f), fmaxf(v[e], 0.f));
+          const float o = conv_act(v[e], a.slope);
           ov[e] = __float_as_uint(o);
           if constexpr (SUMS) ssum[e] += ok[k] ? o : 0.f;
         }

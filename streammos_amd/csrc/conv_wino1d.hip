@@ -239,7 +239,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino1d(Wino1dArgs a) {
           const f32x4 vv = y[e] + bv;
           u32x4 ov;
 #pragma unroll
-          for (int k = 0; k < 4; ++k) ov[k] = __float_as_uint(__builtin_fmaf(a.slope, fminf(vv[k], 0.f), fmaxf(vv[k], 0.f)));
+          for (int k = 0; k < 4; ++k) ov[k] = __float_as_uint(conv_act(vv[k], a.slope));
           const unsigned off = ok ? (unsigned)(((t.b * a.nL * a.nS + gl * a.sL + gs * a.sS) * (int)a.op + c0) * 4) : 0x80000000u;
           __builtin_amdgcn_raw_buffer_store_b128(ov, osrd, off, 0, 0);
         }
