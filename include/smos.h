@@ -103,6 +103,36 @@ int smos_bilinear_gather_bwd(const float* grad_out, const int64_t* grad_out_stri
                              int64_t W, int64_t N, const float* scale, smos_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
+ * Training loss: OHEM cross-entropy + lovasz_weight * Lovasz-softmax (classes = present, one image), one scalar.
+ * Replaces utils/criterion.py:10-28 and utils/lovasz_losses.py:147-222 as AttNet calls them (`ce + 3 * lovasz`).
+ * See csrc/seg_loss.hip.  Nothing is read back: the all-ignored case yields exactly 0 on the device.
+ *   pred    [B, C, P]   float32, element strides pred_stride[3]; C = 2 or 3
+ *   target  [B, P]      int64, contiguous; ignore_index, and any label outside [0, C), takes part as an ignored position
+ *   k                   size of the OHEM top-k, max(int(top_ratio * B * P), 1), from the caller
+ *   coef    [C + 1, B*P] float32 out: rows 0..C-1 the Lovasz coefficient d of each position in class c's sorted order
+ *                       (0 for an ignored position or an absent class), row C the top-k flag (1.0 / 0.0)
+ *   loss    [1]         float32 out
+ *   stats   [2]         float32 out: 1 / number of present classes (0 when there is none), that number
+ *   work                smos_seg_loss_work_bytes(B*P, C) bytes of device scratch (0 from the query: sizes not supported),
+ *                       free again when the call's launches have run
+ * smos_seg_loss_fwd enqueues every launch of the forward (prep, one radix sort over C + 1 segments, tile counts, tile
+ * scan, apply, finish); smos_seg_loss_bwd is one launch that recomputes the softmax and writes
+ *   grad[b, j, p] = grad_out * [ (1/n + top_weight/k * top) * (p_j - [j == y])
+ *                                + lovasz_weight / present * sum_c s_c * coef[c] * p_c * ([c == j] - p_j) ],   s_c = -1 if y == c else 1
+ * (0 at an ignored position) through grad_stride[3]; grad_out is a DEVICE scalar.  Ties between sort keys are broken by
+ * position (a stable sort), sums are float64 partials added in a fixed order: two runs give the same bits.
+ * smos_seg_loss_tile(): elements per block of the scan kernels (tests place their edge cases around it). */
+int32_t smos_seg_loss_tile(void);
+int64_t smos_seg_loss_work_bytes(int64_t n, int32_t C);
+int smos_seg_loss_fwd(const float* pred, const int64_t* pred_stride, const int64_t* target, int64_t B, int32_t C,
+                      int64_t P, int64_t k, float top_weight, float lovasz_weight, int64_t ignore_index, float* coef,
+                      float* loss, float* stats, void* work, int64_t work_bytes, smos_stream_t stream);
+int smos_seg_loss_bwd(const float* pred, const int64_t* pred_stride, const int64_t* target, const float* coef,
+                      const float* stats, const float* grad_out, int64_t B, int32_t C, int64_t P, int64_t k,
+                      float top_weight, float lovasz_weight, int64_t ignore_index, float* grad,
+                      const int64_t* grad_stride, smos_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
  * Multi-scale deformable attention sampler, forward.
  * Replaces MultiScaleDeformableAttention.ms_deform_attn_forward (deformattn/src/vision.cpp:13-16 ->
  * deformattn/src/cuda/ms_deform_attn_cuda.cu:20-80, kernel ms_deform_im2col_cuda.cuh:237-299).

@@ -24,6 +24,10 @@ SIGNATURES = {
     "smos_voxel_maxpool_bwd": [vp, c_i64p, vp, vp, vp, c_i64p, vp, i64, i64, i64, i32, c_i64p, c_f32p, i32, vp],
     "smos_bilinear_gather_fwd": [vp, c_i64p, vp, i32, vp, c_i64p, i64, i64, i64, i64, i64, c_f32p, vp],
     "smos_bilinear_gather_bwd": [vp, c_i64p, vp, i32, vp, c_i64p, i64, i64, i64, i64, i64, c_f32p, vp],
+    "smos_seg_loss_tile": [],
+    "smos_seg_loss_work_bytes": [i64, i32],
+    "smos_seg_loss_fwd": [vp, c_i64p, vp, i64, i32, i64, i64, ctypes.c_float, ctypes.c_float, i64, vp, vp, vp, vp, i64, vp],
+    "smos_seg_loss_bwd": [vp, c_i64p, vp, vp, vp, vp, i64, i32, i64, i64, ctypes.c_float, ctypes.c_float, i64, vp, c_i64p, vp],
     "smos_msda_fwd": [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, vp],
     "smos_msda_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, vp],
     "smos_tta_argmax": [vp, i64, i64, i64, vp, vp, vp],
@@ -126,6 +130,7 @@ def load():
     lib.smos_dbscan_work_bytes.restype = ctypes.c_int64
     lib.smos_instance_work_bytes.restype = ctypes.c_int64
     lib.smos_stem_scan_state_words.restype = ctypes.c_int64
+    lib.smos_seg_loss_work_bytes.restype = ctypes.c_int64
     lib.smos_conv_cl_sum_chunks.restype = ctypes.c_int64
     lib.smos_conv_wino_sum_chunks.restype = ctypes.c_int64
     lib.smos_basic_block_ws_floats.restype = ctypes.c_int64

@@ -216,6 +216,21 @@ SWITCHES = (
     ("block_call", "SMOS_BLOCK_CALL", True, "bool"),          # a residual block = one foreign call (same launches)
 )
 
+# Switches of the training step, in the same row format.  The engine above is inference only, so these become attributes
+# of the model (AttNet.__init__ -> read_switches) and are read there on every call, like the engine's on the engine.
+TRAIN_SWITCHES = (
+    # the "ohem" loss of AttNet._seg_loss as ops.seg_loss (csrc/seg_loss.hip): one fused OHEM-CE + Lovasz value with its own
+    # backward and no host read of a device value.  0: the torch formulation of refapi/models/losses.py
+    ("seg_loss_own", "SMOS_SEG_LOSS", True, "bool"),
+)
+
+
+def read_switches(obj, table):
+    """Set every switch of `table` on `obj` from the environment (or its default)."""
+    for attr, var, default, kind in table:
+        v = os.environ.get(var)
+        setattr(obj, attr, default if v is None else (v != "0" if kind == "bool" else int(v)))
+
 
 class InferenceEngine:
     def __init__(self, net, layout="cl", conv_precision="fp32"):
@@ -234,9 +249,7 @@ class InferenceEngine:
         self._bf16 = conv_precision == "bf16"
         self._conv_layers = {}          # id(folded weight) -> ops.ConvLayer (which holds the weight): see _conv
         self.device = next(net.parameters()).device
-        for attr, var, default, kind in SWITCHES:
-            v = os.environ.get(var)
-            setattr(self, attr, default if v is None else (v != "0" if kind == "bool" else int(v)))
+        read_switches(self, SWITCHES)
         if self._bf16:
             # the block calls launch fp32 kernels: bf16 mode takes the launch-by-launch path
             self.block_call = False

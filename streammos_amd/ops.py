@@ -232,6 +232,92 @@ def bilinear_gather(grid, coord, scale, out=None, point_major=False):
     return _bilinear_gather_fwd(grid, coord, scale, out, point_major)
 
 
+def seg_loss_tile():
+    """Elements per block of the scan kernels of ``seg_loss`` (tests place their edge cases around it)."""
+    return int(_lib.load().smos_seg_loss_tile())
+
+
+def _seg_loss_args(name, pred, target):
+    """-> pred as [B, C, P] (a view, strides kept), target as contiguous int64 [B, P]."""
+    _require_cuda(name, pred, target)
+    if pred.dtype != torch.float32:
+        raise RuntimeError("%s: float32 logits only (got %s)" % (name, pred.dtype))
+    if target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+        raise RuntimeError("%s: integer labels only (got %s)" % (name, target.dtype))
+    if pred.dim() == 4 and pred.shape[3] == 1:
+        pred = pred[..., 0]
+    if target.dim() == 3 and target.shape[2] == 1:
+        target = target[..., 0]
+    if pred.dim() != 3 or target.dim() != 2 or pred.shape[0] != target.shape[0] or pred.shape[2] != target.shape[1]:
+        raise RuntimeError("%s: shape mismatch pred %s target %s (want [B,C,P(,1)] and [B,P(,1)])"
+                           % (name, tuple(pred.shape), tuple(target.shape)))
+    if pred.shape[1] not in (2, 3):
+        raise RuntimeError("%s: %d classes; the kernels are built for C = 2 and C = 3" % (name, pred.shape[1]))
+    if pred.shape[0] * pred.shape[2] == 0:
+        raise RuntimeError("%s: no positions (pred %s)" % (name, tuple(pred.shape)))
+    if target.device != pred.device:
+        raise RuntimeError("%s: pred on %s, target on %s" % (name, pred.device, target.device))
+    return pred, target.to(torch.int64).contiguous()        # labels are small next to the logits; no copy in the usual case
+
+
+class _SegLoss(torch.autograd.Function):
+    """ops.seg_loss: two foreign calls, one per direction.  What the backward needs beyond pred and target is the
+    [C + 1, n] coefficient table and the present-class count, both left on the device by the forward."""
+
+    @staticmethod
+    def forward(ctx, pred, target, k, top_weight, ignore_index, lovasz_weight):
+        p3 = pred[..., 0] if pred.dim() == 4 else pred
+        b, c, p = p3.shape
+        n = b * p
+        lib = _lib.load()
+        need = int(lib.smos_seg_loss_work_bytes(n, c))
+        if need <= 0:
+            raise RuntimeError("seg_loss: %d positions x %d classes is more than the sort is set up for" % (n, c))
+        dev = pred.device
+        work = _stream_workspace("seg_loss", (need,), torch.uint8, dev)
+        coef = torch.empty((c + 1, n), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        stats = torch.empty(2, dtype=torch.float32, device=dev)
+        with _on(dev), profiling.span_f("seg_loss[%dx%dx%d]", (b, c, p)):
+            rc = lib.smos_seg_loss_fwd(p3.data_ptr(), _lib.i64_array(p3.stride()), target.data_ptr(), b, c, p, k, top_weight,
+                                       lovasz_weight, ignore_index, coef.data_ptr(), loss.data_ptr(), stats.data_ptr(),
+                                       work.data_ptr(), need, _stream(pred))
+        _lib.check(rc, "smos_seg_loss_fwd")
+        ctx.save_for_backward(pred, target, coef, stats)
+        ctx.args = (k, float(top_weight), int(ignore_index), float(lovasz_weight))
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        pred, target, coef, stats = ctx.saved_tensors
+        k, top_weight, ignore_index, lovasz_weight = ctx.args
+        grad = torch.empty_like(pred)                 # pred's layout where pred is dense (the point head's view is)
+        p3, g3 = (pred[..., 0], grad[..., 0]) if pred.dim() == 4 else (pred, grad)
+        b, c, p = p3.shape
+        go = grad_out.to(torch.float32).contiguous()
+        lib = _lib.load()
+        with _on(pred.device), profiling.span_f("seg_loss_bwd[%dx%dx%d]", (b, c, p)):
+            rc = lib.smos_seg_loss_bwd(p3.data_ptr(), _lib.i64_array(p3.stride()), target.data_ptr(), coef.data_ptr(),
+                                       stats.data_ptr(), go.data_ptr(), b, c, p, k, top_weight, lovasz_weight, ignore_index,
+                                       g3.data_ptr(), _lib.i64_array(g3.stride()), _stream(pred))
+        _lib.check(rc, "smos_seg_loss_bwd")
+        return grad, None, None, None, None, None
+
+
+def seg_loss(pred, target, top_ratio=0.2, top_weight=4.0, ignore_index=0, lovasz_weight=3.0):
+    """``ohem_cross_entropy(pred, target, top_ratio, top_weight, ignore_index) + lovasz_weight * lovasz_softmax(pred, target,
+    ignore=ignore_index)`` of refapi/models/losses.py as one 0-dim device tensor, differentiable in ``pred``
+    (csrc/seg_loss.hip).  pred [B,C,P(,1)] float32 with any strides (read in place), C = 2 or 3; target [B,P(,1)] integer.
+    Nothing is read back to the host in either direction: where every label is ignored the result is a zero tensor (the
+    torch formulation returns the int 0 there) and the gradient is all zeros."""
+    pred3, tgt = _seg_loss_args("seg_loss", pred, target)
+    k = max(int(top_ratio * (pred3.shape[0] * pred3.shape[2])), 1)
+    if torch.is_grad_enabled() and pred.requires_grad:
+        return _SegLoss.apply(pred, tgt, k, float(top_weight), int(ignore_index), float(lovasz_weight))
+    with torch.no_grad():
+        return _SegLoss.apply(pred3, tgt, k, float(top_weight), int(ignore_index), float(lovasz_weight))
+
+
 def msda_fwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight):
     """value [N,S,M,D], shapes [L,2] int64 (device), level_start [L] int64 (device), loc [N,Lq,M,L,P,2],
     attn [N,Lq,M,L,P] -> [N,Lq,M*D]."""

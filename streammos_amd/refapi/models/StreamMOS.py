@@ -41,6 +41,8 @@ class AttNet(nn.Module):
         self.engine_conv_precision = "fp32"     # "fp32" (default, exact) or "bf16" (opt-in bf16 matrix-core convolutions)
         self.engine_miopen_search = True
         self._engine = None
+        from ... import engine
+        engine.read_switches(self, engine.TRAIN_SWITCHES)      # seg_loss_own (SMOS_SEG_LOSS): read on every _seg_loss call
 
     def build_network(self):
         p = self.pModel
@@ -128,6 +130,11 @@ class AttNet(nn.Module):
     def _seg_loss(self, pred, target):
         from . import losses
         mode = self.pModel.loss_mode
+        if (mode == "ohem" and self.seg_loss_own and pred.is_cuda and pred.dtype == torch.float32 and pred.dim() in (3, 4)
+                and pred.shape[1] <= 3):
+            # OHEM-CE + 3 * Lovasz as one device-resident value with its own backward (csrc/seg_loss.hip): no host read
+            from ... import ops
+            return ops.seg_loss(pred, target, top_ratio=0.2, top_weight=4.0, ignore_index=0, lovasz_weight=3.0)
         if mode == "ohem":
             ce = losses.ohem_cross_entropy(pred, target, top_ratio=0.2, top_weight=4.0, ignore_index=0)
         elif mode == "ce":
