@@ -41,7 +41,8 @@ int smos_abi_version(void);
 const char* smos_last_error(void);
 /* Test hook (process-wide, not part of the data path; the one piece of state the library keeps): caps the grid of the
  * persistent convolution kernels (smos_conv_cl / _rows_cl / _wino_cl / _wino1d_cl / _bf16_cl), of smos_stem_gemm, of
- * smos_pointnet_scatter / _rows / _rows_live and of smos_gather_scatter_cl / _live / _view at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
+ * smos_pointnet_scatter / _rows / _rows_live, of smos_gather_scatter_cl / _live / _view and of the emit, copy, start and sum
+ * kernels of smos_bilinear_gather_bwd_det / smos_msda_bwd_det at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
  * item-boundary code paths, a wave's whole-tile / head / tail units of the stem, the scatter's software pipeline -- on shapes
  * small enough to check against float64.  The results do not depend on it. */
 int smos_debug_set_conv_grid_cap(int32_t blocks);
@@ -101,6 +102,24 @@ int smos_bilinear_gather_fwd(const float* grid, const int64_t* grid_stride, cons
 int smos_bilinear_gather_bwd(const float* grad_out, const int64_t* grad_out_stride, const float* coord, int32_t K,
                              float* grad_grid, const int64_t* grad_grid_stride, int64_t B, int64_t C, int64_t H,
                              int64_t W, int64_t N, const float* scale, smos_stream_t stream);
+
+/* The same gradient summed in a FIXED order, without atomics on the data (csrc/segsum.hip): every (point, tap) pair is
+ * written out with its destination row (b * H + y) * W + x as a 32-bit key, one stable radix sort brings the pairs of a
+ * row together in ascending pair index (b * N + n) * 4 + k, k = nw, ne, sw, se, and a row is then summed as a defined
+ * float32 number: term j = w_j * grad_out_j (one rounding); chunks of smos_segsum_chunk() consecutive terms are summed
+ * left to right from their first term; the chunk partials are added left to right (round-to-nearest additions, no FMA).
+ * A pixel no pair reaches is exactly 0.  Two calls give the same bits, on any grid and any device.
+ * Arguments as smos_bilinear_gather_bwd (any strides on both tensors; grad_grid may arrive uninitialised), then
+ *   work   smos_bilinear_gather_bwd_det_work_bytes(B, C, H, W, N) bytes of device scratch, 256-byte aligned, free again
+ *          when the call's launches have run.  The query returns 0 for an empty problem (no scratch is touched) and -1
+ *          where the 32-bit keys do not reach: it needs B * N < 2^29 and B * H * W < 2^31 - 1.
+ * Float32 only. */
+int32_t smos_segsum_chunk(void);
+int64_t smos_bilinear_gather_bwd_det_work_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t N);
+int smos_bilinear_gather_bwd_det(const float* grad_out, const int64_t* grad_out_stride, const float* coord, int32_t K,
+                                 float* grad_grid, const int64_t* grad_grid_stride, int64_t B, int64_t C, int64_t H,
+                                 int64_t W, int64_t N, const float* scale, void* work, int64_t work_bytes,
+                                 smos_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * Training loss: OHEM cross-entropy + lovasz_weight * Lovasz-softmax (classes = present, one image), one scalar.
@@ -509,6 +528,20 @@ int smos_msda_bwd(const void* grad_out, const void* value, const int64_t* spatia
                   const void* sampling_loc, const void* attn_weight, void* grad_value, void* grad_sampling_loc,
                   void* grad_attn_weight, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
                   int32_t dtype, smos_stream_t stream);
+
+/* smos_msda_bwd for float32 with grad_value summed in a fixed order (csrc/segsum.hip; the scheme and the definition of
+ * the sum are those of smos_bilinear_gather_bwd_det).  Pair index ((((b * Lq + q) * M + m) * L + l) * P + p) * 4 + corner,
+ * corners in the order of the atomic kernel (top-left, top-right, bottom-left, bottom-right); key = the row
+ * (b * S + level_start[l] + y * W + x) * M + m of grad_value; pair weight (w_y * w_x) * attn, two float32 products in that
+ * order; term = weight * grad_out[b, q, m, :].  grad_value may arrive uninitialised and is fully written (0 where no
+ * sample reaches).  grad_sampling_loc and grad_attn_weight come from the arithmetic of smos_msda_bwd: the same bits.
+ *   work   smos_msda_bwd_det_work_bytes(N, S, M, D, L, Lq, P) bytes of device scratch, 256-byte aligned (0: an empty
+ *          problem, -1: more than 2^29 - 1 samples or 2^31 - 2 value rows). */
+int64_t smos_msda_bwd_det_work_bytes(int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P);
+int smos_msda_bwd_det(const float* grad_out, const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                      const float* sampling_loc, const float* attn_weight, float* grad_value, float* grad_sampling_loc,
+                      float* grad_attn_weight, int64_t N, int64_t S, int64_t M, int64_t D, int64_t L, int64_t Lq, int64_t P,
+                      void* work, int64_t work_bytes, smos_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * Channels-last ("cl") engine kernels (csrc/cl_kernels.hip).  A map is [B, H, W, C] with C innermost; every tensor

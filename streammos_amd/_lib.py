@@ -24,12 +24,17 @@ SIGNATURES = {
     "smos_voxel_maxpool_bwd": [vp, c_i64p, vp, vp, vp, c_i64p, vp, i64, i64, i64, i32, c_i64p, c_f32p, i32, vp],
     "smos_bilinear_gather_fwd": [vp, c_i64p, vp, i32, vp, c_i64p, i64, i64, i64, i64, i64, c_f32p, vp],
     "smos_bilinear_gather_bwd": [vp, c_i64p, vp, i32, vp, c_i64p, i64, i64, i64, i64, i64, c_f32p, vp],
+    "smos_segsum_chunk": [],
+    "smos_bilinear_gather_bwd_det_work_bytes": [i64, i64, i64, i64, i64],
+    "smos_bilinear_gather_bwd_det": [vp, c_i64p, vp, i32, vp, c_i64p, i64, i64, i64, i64, i64, c_f32p, vp, i64, vp],
     "smos_seg_loss_tile": [],
     "smos_seg_loss_work_bytes": [i64, i32],
     "smos_seg_loss_fwd": [vp, c_i64p, vp, i64, i32, i64, i64, ctypes.c_float, ctypes.c_float, i64, vp, vp, vp, vp, i64, vp],
     "smos_seg_loss_bwd": [vp, c_i64p, vp, vp, vp, vp, i64, i32, i64, i64, ctypes.c_float, ctypes.c_float, i64, vp, c_i64p, vp],
     "smos_msda_fwd": [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, vp],
     "smos_msda_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, vp],
+    "smos_msda_bwd_det_work_bytes": [i64, i64, i64, i64, i64, i64, i64],
+    "smos_msda_bwd_det": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, vp, i64, vp],
     "smos_tta_argmax": [vp, i64, i64, i64, vp, vp, vp],
     "smos_vote_clear": [vp, vp],
     "smos_vote_accumulate": [vp, i64, i64, vp, c_f64p, i32, vp, vp],
@@ -131,6 +136,8 @@ def load():
     lib.smos_instance_work_bytes.restype = ctypes.c_int64
     lib.smos_stem_scan_state_words.restype = ctypes.c_int64
     lib.smos_seg_loss_work_bytes.restype = ctypes.c_int64
+    lib.smos_bilinear_gather_bwd_det_work_bytes.restype = ctypes.c_int64
+    lib.smos_msda_bwd_det_work_bytes.restype = ctypes.c_int64
     lib.smos_conv_cl_sum_chunks.restype = ctypes.c_int64
     lib.smos_conv_wino_sum_chunks.restype = ctypes.c_int64
     lib.smos_basic_block_ws_floats.restype = ctypes.c_int64

@@ -142,6 +142,35 @@ def voxel_maxpool_bwd(feat, ind, out, grad_out, grad_feat, out_size, scale):
     return grad_feat
 
 
+_deterministic = None
+
+
+def set_deterministic(flag):
+    """Explicit setting of ``is_deterministic`` (True / False), or None to hand the decision back to the environment.
+    Returns the previous explicit setting."""
+    global _deterministic
+    prev, _deterministic = _deterministic, (None if flag is None else bool(flag))
+    return prev
+
+
+def is_deterministic():
+    """Whether ``bilinear_gather_backward`` and ``msda_bwd`` (and so the autograd nodes over them) sum in a fixed order
+    (csrc/segsum.hip) when their ``deterministic`` argument is None.  Resolved on every call: the explicit
+    ``set_deterministic`` setting if there is one, else ``SMOS_DETERMINISTIC`` in the environment if it is set (default 0),
+    else ``torch.are_deterministic_algorithms_enabled()``."""
+    if _deterministic is not None:
+        return _deterministic
+    env = os.environ.get("SMOS_DETERMINISTIC")
+    if env is not None and env != "":
+        return env != "0"
+    return bool(torch.are_deterministic_algorithms_enabled())
+
+
+def segsum_chunk():
+    """Terms per chunk of the fixed-order sums (tests place their edge cases around it)."""
+    return int(_lib.load().smos_segsum_chunk())
+
+
 def _bilinear_gather_fwd(grid, coord, scale, out, point_major):
     if coord.dim() == 4:
         coord = coord[..., 0]
@@ -163,14 +192,17 @@ def _bilinear_gather_fwd(grid, coord, scale, out, point_major):
     return out
 
 
-def bilinear_gather_backward(grad_out, coord, scale, grid_shape, channels_last=True):
+def bilinear_gather_backward(grad_out, coord, scale, grid_shape, channels_last=True, deterministic=None):
     """Gradient of ``bilinear_gather`` with respect to its grid (csrc/bilinear_gather.hip, smos_bilinear_gather_bwd).
 
     grad_out [B,C,N] (any strides: channel-major from the module graph, point-major from a point-major forward),
     coord [B,N,K(,1)], grid_shape (B,C,H,W) or (H,W) -> grad_grid [B,C,H,W].  With ``channels_last`` the result is a
     permuted view of a [B,H,W,C] buffer, which the kernel adds to in whole rows; otherwise it is NCHW-contiguous and
     every (point, tap, channel) is a 4-byte atomic.  The kernel zeroes the result itself.  The sums are float atomics:
-    their last bits depend on arrival order."""
+    their last bits depend on arrival order.
+
+    ``deterministic`` (None: ``is_deterministic()``): the store-and-sum form smos_bilinear_gather_bwd_det of csrc/segsum.hip
+    instead, for either layout of the result: no atomics, a defined float32 sum per element, the same bits on every run."""
     _require_cuda("bilinear_gather_backward", grad_out, coord)
     if grad_out.dtype != torch.float32 or coord.dtype != torch.float32:
         raise RuntimeError("bilinear_gather_backward: float32 only (got %s, %s)" % (grad_out.dtype, coord.dtype))
@@ -191,6 +223,18 @@ def bilinear_gather_backward(grad_out, coord, scale, grid_shape, channels_last=T
     else:
         grad_grid = torch.empty((b, c, h, w), dtype=torch.float32, device=grad_out.device)
     lib = _lib.load()
+    if is_deterministic() if deterministic is None else deterministic:
+        need = int(lib.smos_bilinear_gather_bwd_det_work_bytes(b, c, h, w, n))
+        if need < 0:
+            raise RuntimeError("bilinear_gather_backward: the deterministic form takes B * N < 2^29 points and B * H * W < 2^31 - 1 "
+                               "pixels (got %d, %d)" % (b * n, b * h * w))
+        with _on(grad_out.device), profiling.span_f("bilinear_gather_bwd_det[%dx%dx%dx%d<-%d]", (b, c, h, w, n)):
+            work = torch.empty((need,), dtype=torch.uint8, device=grad_out.device)     # on the current stream, like grad_grid
+            rc = lib.smos_bilinear_gather_bwd_det(grad_out.data_ptr(), _lib.i64_array(grad_out.stride()), coord.data_ptr(), k,
+                                                  grad_grid.data_ptr(), _lib.i64_array(grad_grid.stride()), b, c, h, w, n,
+                                                  _lib.f32_array(scale), work.data_ptr(), need, _stream(grad_out))
+        _lib.check(rc, "smos_bilinear_gather_bwd_det")
+        return grad_grid
     with _on(grad_out.device), profiling.span_f("bilinear_gather_bwd[%dx%dx%dx%d<-%d]", (b, c, h, w, n)):
         rc = lib.smos_bilinear_gather_bwd(grad_out.data_ptr(), _lib.i64_array(grad_out.stride()), coord.data_ptr(), k,
                                           grad_grid.data_ptr(), _lib.i64_array(grad_grid.stride()), b, c, h, w, n,
@@ -338,18 +382,44 @@ def msda_fwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight
     return out
 
 
-def msda_bwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output):
-    """Returns (grad_value, grad_sampling_loc, grad_attn_weight)."""
+def msda_bwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, deterministic=None):
+    """Returns (grad_value, grad_sampling_loc, grad_attn_weight).
+
+    ``deterministic`` (None: ``is_deterministic()``): grad_value summed in a fixed order by smos_msda_bwd_det
+    (csrc/segsum.hip) instead of float atomics; the other two gradients are the same bits either way.  The fixed-order
+    form is float32 only: float64 inputs stay on the atomic kernel under an ambient setting (None), and raise when
+    ``deterministic=True`` is asked for explicitly."""
+    det = is_deterministic() if deterministic is None else bool(deterministic)
+    if det and value.dtype != torch.float32:
+        if deterministic is not None:
+            raise RuntimeError("ms_deform_attn_backward: the deterministic form is float32 only (got %s)" % value.dtype)
+        det = False
     _require_cuda("ms_deform_attn_backward", value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output)
     for name, t in (("value", value), ("sampling_loc", sampling_loc), ("attn_weight", attn_weight), ("grad_output", grad_output)):
         if not t.is_contiguous():
             raise RuntimeError("%s tensor has to be contiguous" % name)
     n, s, m, d = value.shape
     lq, l, p = sampling_loc.shape[1], sampling_loc.shape[3], sampling_loc.shape[4]
-    g_value = torch.zeros_like(value)
+    g_value = torch.empty_like(value) if det else torch.zeros_like(value)      # the fixed-order form writes every element
     g_loc = torch.empty_like(sampling_loc)
     g_attn = torch.empty_like(attn_weight)
     lib = _lib.load()
+    if det:
+        for name, t in (("sampling_loc", sampling_loc), ("attn_weight", attn_weight), ("grad_output", grad_output)):
+            if t.dtype != torch.float32:
+                raise RuntimeError("ms_deform_attn_backward: %s is %s, value float32" % (name, t.dtype))
+        need = int(lib.smos_msda_bwd_det_work_bytes(n, s, m, d, l, lq, p))
+        if need < 0:
+            raise RuntimeError("ms_deform_attn_backward: the deterministic form takes fewer than 2^29 samples and 2^31 - 1 value "
+                               "rows (got %d, %d)" % (n * lq * m * l * p, n * s * m))
+        with _on(value.device), profiling.span_f("msda_bwd_det[%dx%dx%dx%d]", (n, lq, m, d)):
+            work = torch.empty((need,), dtype=torch.uint8, device=value.device)
+            rc = lib.smos_msda_bwd_det(grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(),
+                                       level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+                                       g_value.data_ptr(), g_loc.data_ptr(), g_attn.data_ptr(), n, s, m, d, l, lq, p,
+                                       work.data_ptr(), need, _stream(value))
+        _lib.check(rc, "smos_msda_bwd_det")
+        return g_value, g_loc, g_attn
     with _on(value.device), profiling.span_f("msda_bwd[%dx%dx%dx%d]", (n, lq, m, d)):
         rc = lib.smos_msda_bwd(grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
                                sampling_loc.data_ptr(), attn_weight.data_ptr(), g_value.data_ptr(), g_loc.data_ptr(),
