@@ -35,7 +35,8 @@
 //
 // Arithmetic: plain fp32 (exact products, fp32 accumulation in k order per tile), LayerNorm two-pass (mean, then centred
 // variance; biased; eps inside the root) like torch's.  Against the float64 formulation: <= 2e-6 of the output range
-// (tests/test_gpu_ops.py::test_tfusion_*).
+// (tests/test_gpu_ops.py::test_tfusion_*); per steered row group, at every FFN width, token count and pitch at which the
+// kernels take another path, against a float32 restatement of this order: tests/test_gpu_tfusion.py.
 #include "conv_common.h"
 
 // Diagnostic build only (tools/tf_stamps.py, -DSMOS_TF_STAMPS): s_memtime stamps of wave 0 of every block at the phase

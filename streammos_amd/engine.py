@@ -399,7 +399,7 @@ class InferenceEngine:
     @staticmethod
     def _add_norm(a, b, norm, c):
         """LayerNorm(a + b) in one pass (csrc/epilogue.hip) for the token widths that kernel is built for."""
-        if c % 64 == 0 and c <= 512:
+        if c in (64, 128, 256, 512):
             return ops.add_layer_norm(a.contiguous(), b.contiguous(), norm[0], norm[1], norm[2] if len(norm) > 2 else 1e-5)
         return F.layer_norm(a + b, (c,), norm[0], norm[1], norm[2] if len(norm) > 2 else 1e-5)
 
