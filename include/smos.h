@@ -42,7 +42,7 @@ const char* smos_last_error(void);
 /* Test hook (process-wide, not part of the data path; the one piece of state the library keeps): caps the grid of the
  * persistent convolution kernels (smos_conv_cl / _rows_cl / _wino_cl / _wino1d_cl / _bf16_cl), of smos_stem_gemm, of
  * smos_pointnet_scatter / _rows / _rows_live, of smos_gather_scatter_cl / _live / _view and of the emit, copy, start and sum
- * kernels of smos_bilinear_gather_bwd_det / smos_msda_bwd_det at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
+ * kernels of smos_bilinear_gather_bwd_det / smos_msda_bwd_det and of smos_train_prep_build / _draws at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
  * item-boundary code paths, a wave's whole-tile / head / tail units of the stem, the scatter's software pipeline -- on shapes
  * small enough to check against float64.  The results do not depend on it. */
 int smos_debug_set_conv_grid_cap(int32_t blocks);
@@ -518,6 +518,51 @@ int smos_prep_emit(const float* moved, const int32_t* mask, const int32_t* prefi
 /* raw[i] = mask[i] ? labels[prefix[i]-1] : 0   (val_StreamMOS.py:112-118) */
 int smos_prep_unpad_labels(const uint8_t* labels, int64_t N, const int32_t* mask, const int32_t* prefix, int64_t n,
                            uint8_t* raw, smos_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
+ * Device-side training sample builder (csrc/train_prep.hip): what DataloadTrain.__getitem__
+ * does with numpy per sample (datasets/data_StreamMOS.py:292-364, datasets/utils.py:116-126,280-343) without copy-paste:
+ * 5 scans -> 3 chained windows of 3 frames (window w, frame t = scan w + t), each aligned (twice for w > 0, one float32
+ * rounding per alignment), range-filtered, resampled with replacement to N points, augmented, quantised; the targets of
+ * frame 0 and its BEV label grid.  range6 / bev_size3 / rv4 as in the validation block above.  Four launches, no host read.
+ *
+ *   scans[5], label_words[5]  host arrays of device pointers: [n_k, 4] float32 rows (16-byte aligned), [n_k] uint32 words
+ *   n[5]                      host, 1 <= n_k <= 2^30
+ *   first_pose  [5][16]       host doubles, inv(P_0) P_k row-major (applied to every scan, frame 0 included)
+ *   second_pose [3][16]       host doubles, inv(P_w) P_0 (entry 0 is not read)
+ *   words, noise              device draws, uint32 [3, 3, N] and float64 [3, 3*N, 3], or both NULL: the seeded generator
+ *   seed, sample_index, noise_mean, noise_std   read by the seeded generator only
+ *   shift3, scale, v_flip, h_flip, rot_cos, rot_sin   the sample's augmentation scalars (host); shift and scale are rounded
+ *                             to float32, cos / sin of theta_z * pi / 180 stay float64; v_flip negates x, h_flip negates y
+ *   lut [n_maps][lut_len]     device int32; target m = lut[m][word & 0xFFFF], 0 for an id >= lut_len; 1 <= n_maps <= 4
+ *   xyzi[3], coord[3], sphere[3]   host arrays of device pointers, per window: [3,7,N], [3,N,3], [3,N,2] float32
+ *   targets[n_maps * 3]       device pointers [N] int64, entry m * 3 + w
+ *   bev[3]                    device pointers [bev_size3[0]/2, bev_size3[1]/2] int64: max label of map 0 over the cells
+ *                             (int)(x_quan * 0.5), (int)(y_quan * 0.5) of frame 0 with the cell rule of
+ *                             smos_voxel_maxpool_fwd, empty cell 0; zero-filled here
+ *   counts [9]                device int32: in-range points of job 3 w + t.  A job with none is written as the validation
+ *                             padding point (-1000, -1000, -4000, -1000) with label 0 (the reference raises there)
+ *   work                      smos_train_prep_work_bytes(max n_k) bytes of device scratch, 256-byte aligned (-1: bad size)
+ * Resampling: slot j takes kept point ((uint64)r * n_valid) >> 32 of its 32-bit draw r.
+ * Augmentation per slot: p = f32(f64(p) + noise); p += f32(shift); p *= f32(scale); flips;
+ *   x' = f32(f64(x) * cos + f64(y) * sin), y' = f32(f64(y) * cos - f64(x) * sin).  Out-of-range results are kept.
+ * Seeded draws: Philox4x32-10, key = (seed low word, seed high word), counter = (j, call << 16 | w << 8 | t,
+ *   sample_index low word, sample_index high word).  Call 0 yields (r, unused, x1, x2), call 1 yields (y1, y2, z1, z2);
+ *   noise_d = f64(f32(z_d * f32(noise_std)) + f32(noise_mean)) with the float32 Box-Muller
+ *   z_d = sqrt(-2 ln(((d1 >> 8) + 1) * 2^-24)) * cos(2 pi * (d2 >> 8) * 2^-24).
+ * The results depend on neither the grid size nor smos_debug_set_conv_grid_cap, which caps these launches too. */
+int64_t smos_train_prep_work_bytes(int64_t n_max);
+int smos_train_prep_build(const void* const* scans, const void* const* label_words, const int64_t* n, const double* first_pose,
+                          const double* second_pose, const double* range6, const int64_t* bev_size3, const double* rv4,
+                          int64_t N, const uint32_t* words, const double* noise, uint64_t seed, uint64_t sample_index,
+                          double noise_mean, double noise_std, const double* shift3, double scale, int32_t v_flip,
+                          int32_t h_flip, double rot_cos, double rot_sin, const int32_t* lut, int32_t n_maps, int32_t lut_len,
+                          void* const* xyzi, void* const* coord, void* const* sphere, void* const* targets, void* const* bev,
+                          int32_t* counts, void* work, int64_t work_bytes, smos_stream_t stream);
+/* words [3, 3, N] uint32 and noise [3, 3*N, 3] float64 (device): exactly what smos_train_prep_build generates for
+ * (seed, sample_index) when it is given no draws. */
+int smos_train_prep_draws(uint64_t seed, uint64_t sample_index, int64_t N, double noise_mean, double noise_std,
+                          uint32_t* words, double* noise, smos_stream_t stream);
 
 /* Multi-scale deformable attention, backward (training row f2).  Replaces
  * MultiScaleDeformableAttention.ms_deform_attn_backward (deformattn/src/cuda/ms_deform_attn_cuda.cu:83-153, kernels

@@ -86,6 +86,12 @@ SIGNATURES = {
     "smos_prep_transform_mask": [vp, i64, c_f64p, c_f64p, vp, vp, vp],
     "smos_prep_emit": [vp, vp, vp, i64, i32, i32, i64, i32, c_f32p, c_f32p, c_f64p, c_i64p, c_f64p, vp, vp, vp, vp],
     "smos_prep_unpad_labels": [vp, i64, vp, vp, i64, vp, vp],
+    "smos_train_prep_work_bytes": [i64],
+    "smos_train_prep_build": [ctypes.POINTER(vp), ctypes.POINTER(vp), c_i64p, c_f64p, c_f64p, c_f64p, c_i64p, c_f64p, i64, vp, vp,
+                              ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double, ctypes.c_double, c_f64p, ctypes.c_double, i32, i32,
+                              ctypes.c_double, ctypes.c_double, vp, i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp),
+                              ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, i64, vp],
+    "smos_train_prep_draws": [ctypes.c_uint64, ctypes.c_uint64, i64, ctypes.c_double, ctypes.c_double, vp, vp, vp],
     "smos_bias_act_cl": [vp, i64, vp, vp, i64, vp, i64, i64, i64, i32, vp],
     "smos_downsample_epilogue_cl": [vp, i64, vp, i64, vp, vp, i64, i64, i64, i64, i64, i32, vp],
     "smos_channel_gate_residual_cl": [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, vp],
@@ -138,6 +144,7 @@ def load():
     lib.smos_seg_loss_work_bytes.restype = ctypes.c_int64
     lib.smos_bilinear_gather_bwd_det_work_bytes.restype = ctypes.c_int64
     lib.smos_msda_bwd_det_work_bytes.restype = ctypes.c_int64
+    lib.smos_train_prep_work_bytes.restype = ctypes.c_int64
     lib.smos_conv_cl_sum_chunks.restype = ctypes.c_int64
     lib.smos_conv_wino_sum_chunks.restype = ctypes.c_int64
     lib.smos_basic_block_ws_floats.restype = ctypes.c_int64

@@ -5,6 +5,8 @@ arithmetic).  Only the raw scans cross PCIe; compaction, padding, TTA flips, qua
 computed by csrc/preprocess.hip.  No host synchronisation: the number of in-range points stays on the device (the
 un-padding of the labels is a kernel too).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -95,3 +97,254 @@ class DevicePreprocessor:
                                                   built["prefix"].data_ptr(), built["n_raw"], raw.data_ptr(),
                                                   torch.cuda.current_stream(self.device).cuda_stream), "smos_prep_unpad_labels")
         return raw
+
+
+def check_train_counts(counts):
+    """Host copy of ``in_range_counts`` [B, 3, T] -> the error of the host path's reference (``np.random.choice`` raises on an
+    empty frame) for a (sample, window, frame) without in-range points."""
+    counts = np.asarray(counts).reshape(-1, preprocess.TRAIN_WINDOWS, preprocess.TRAIN_FRAMES - preprocess.TRAIN_WINDOWS + 1)
+    for b, w, t in zip(*np.nonzero(counts == 0)):
+        raise ValueError("sample %d, window %d, frame %d has no point inside the range: nothing to resample from (the frame "
+                         "was written as the padding point with label 0)" % (b, w, t))
+
+
+class DeviceTrainPreprocessor:
+    """Training samples built on the device (row f2, csrc/train_prep.hip): raw scans, label words and poses in, the batch dict
+    of ``AttNet.forward`` out.  Host equivalent: ``streammos_amd.preprocess.build_train_sample``.  Only the scans (16 bytes a
+    point) and label words (4 bytes a point) cross PCIe; nothing is read back, the per-frame in-range counts stay on the device
+    (``check_counts`` is the one synchronising call).  Copy-paste augmentation is host work done before this call: the
+    builder takes scans and label words as they are.
+
+    The random draws are either explicit (``preprocess.TrainDraws`` with device or host ``words`` / ``noise``) or come from a
+    seed: Philox4x32-10 inside the kernels for the resampling words and the noise, ``preprocess.seeded_scalars`` on the host
+    for the five per-sample scalars.  The same (seed, sample_index) gives the same bits on every run."""
+
+    T = preprocess.TRAIN_FRAMES - preprocess.TRAIN_WINDOWS + 1
+    W = preprocess.TRAIN_WINDOWS
+
+    def __init__(self, device, spec=None, frame_point_num=130000, aug=None, label_maps=None):
+        from . import kitti
+        self.device = torch.device(device)
+        self.spec = spec or preprocess.VoxelSpec()
+        self.N = int(frame_point_num)
+        if self.N <= 0:
+            raise RuntimeError("DeviceTrainPreprocessor: frame_point_num must be positive, got %d" % self.N)
+        self.aug = aug or preprocess.AugParam()
+        maps = dict(label_maps or {"pcds_target": kitti.learning_map_lut()})
+        if not 1 <= len(maps) <= 4:
+            raise RuntimeError("DeviceTrainPreprocessor: 1..4 label maps, got %d" % len(maps))
+        self.target_names = list(maps)
+        lut_len = max(int(np.asarray(m).shape[0]) for m in maps.values())
+        lut = np.zeros((len(maps), lut_len), dtype=np.int32)
+        for i, m in enumerate(maps.values()):
+            lut[i, :np.asarray(m).shape[0]] = np.asarray(m)
+        self._lut = torch.from_numpy(lut).to(self.device)
+        sp = self.spec
+        self._range6 = _lib.f64_array([sp.range_x[0], sp.range_x[1], sp.range_y[0], sp.range_y[1], sp.range_z[0], sp.range_z[1]])
+        self._bev3 = _lib.i64_array(sp.bev_shape)
+        self.bev_target_shape = (sp.bev_shape[0] // 2, sp.bev_shape[1] // 2, 1)
+        h, w = sp.rv_shape
+        phi_hi, phi_lo = 180.0 * np.pi / 180.0, -180.0 * np.pi / 180.0          # datasets/utils.py:176
+        th_lo, th_hi = sp.RV_theta[0] * np.pi / 180.0, sp.RV_theta[1] * np.pi / 180.0
+        self._rv4 = _lib.f64_array([phi_hi, (phi_hi - phi_lo) / w, th_hi, (th_hi - th_lo) / h])
+        self._work = {}            # stream -> scratch tensor (a stream runs its builds one after the other)
+
+    # ---- buffers ----------------------------------------------------------------------------------------------------------
+    def output_shapes(self):
+        n = self.N
+        shapes = {}
+        for i in range(self.W):
+            shapes["pcds_xyzi_%d" % i] = ((self.T, 7, n, 1), torch.float32)
+            shapes["pcds_coord_%d" % i] = ((self.T, n, 3, 1), torch.float32)
+            shapes["pcds_sphere_coord_%d" % i] = ((self.T, n, 2, 1), torch.float32)
+            shapes["pcds_bev_target_%d" % i] = (self.bev_target_shape, torch.int64)
+            for name in self.target_names:
+                shapes["%s_%d" % (name, i)] = ((n, 1), torch.int64)
+        shapes["in_range_counts"] = ((self.W, self.T), torch.int32)
+        return shapes
+
+    def alloc_batch(self, batch_size):
+        """Uninitialised batch tensors (leading batch dimension) that ``build(out=..., batch_slot=b)`` fills slice by slice."""
+        return {k: torch.empty((int(batch_size),) + tuple(shape), dtype=dtype, device=self.device)
+                for k, (shape, dtype) in self.output_shapes().items()}
+
+    def _stage(self, arrays, dtype):
+        """Host arrays -> one device tensor through pinned staging (one copy; the pinned block goes back to torch's caching
+        host allocator, which re-uses it only after the copy has run: no host wait)."""
+        total = sum(a.shape[0] for a in arrays)
+        staged = torch.empty((total,) + tuple(arrays[0].shape[1:]), dtype=dtype, pin_memory=True)
+        at = 0
+        for a in arrays:
+            staged[at:at + a.shape[0]].copy_(torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a))
+            at += a.shape[0]
+        return staged.to(self.device, non_blocking=True)
+
+    def _check_rows(self, items, what, np_dtypes, torch_dtypes, trailing):
+        if len(items) != preprocess.TRAIN_FRAMES:
+            raise RuntimeError("DeviceTrainPreprocessor: a training sample has %d %s, got %d" % (preprocess.TRAIN_FRAMES, what, len(items)))
+        on_dev = [torch.is_tensor(s) and s.is_cuda for s in items]
+        for s, dev in zip(items, on_dev):
+            shape_ok = getattr(s, "ndim", None) == 1 + len(trailing) and tuple(s.shape[1:]) == trailing and s.shape[0] >= 1
+            if dev:
+                ok = s.dtype in torch_dtypes and s.is_contiguous() and s.device == self.device
+            else:
+                ok = isinstance(s, np.ndarray) and s.dtype in np_dtypes and s.flags["C_CONTIGUOUS"]
+            if not (ok and shape_ok):
+                raise RuntimeError("DeviceTrainPreprocessor: %s must be contiguous %s arrays of shape [n >= 1%s], on the host (numpy) "
+                                   "or on %s" % (what, np_dtypes[0].__name__, "".join(", %d" % d for d in trailing), self.device))
+
+    def _device_rows(self, items, torch_dtype, trailing):
+        """Five checked host arrays or device tensors -> (device pointers, lengths, tensors kept alive).  The host arrays
+        among them go up in one copy; a device tensor is used where it lies."""
+        lengths = [int(s.shape[0]) for s in items]
+        host = [s for s in items if not torch.is_tensor(s)]
+        keep = [s for s in items if torch.is_tensor(s)]
+        ptrs = [s.data_ptr() if torch.is_tensor(s) else None for s in items]
+        if host:
+            whole = self._stage(host, torch_dtype)
+            keep.append(whole)
+            step = whole.element_size() * int(np.prod(trailing, dtype=np.int64))
+            at = 0
+            for i, s in enumerate(items):
+                if ptrs[i] is None:
+                    ptrs[i] = whole.data_ptr() + at * step
+                    at += lengths[i]
+        return ptrs, lengths, keep
+
+    def _check_draw(self, value, what, shape, np_dtype, torch_dtypes):
+        if torch.is_tensor(value) and value.is_cuda:
+            ok = value.dtype in torch_dtypes and value.is_contiguous() and tuple(value.shape) == shape and value.device == self.device
+        else:
+            ok = isinstance(value, np.ndarray) and value.dtype == np_dtype and value.shape == shape
+        if not ok:
+            raise RuntimeError("DeviceTrainPreprocessor: draws.%s must be %s of shape %s, on the host (numpy) or on %s"
+                               % (what, np.dtype(np_dtype).name, list(shape), self.device))
+
+    def _draw_tensor(self, value, shape, torch_dtype):
+        if torch.is_tensor(value):
+            return value
+        return self._stage([np.ascontiguousarray(value).reshape((1,) + shape)], torch_dtype)
+
+    # ---- draws ------------------------------------------------------------------------------------------------------------
+    def seeded_draws(self, seed, sample_index=0):
+        """The draws ``build(seed=seed, sample_index=sample_index)`` uses, as explicit ``TrainDraws`` with device tensors:
+        smos_train_prep_draws for the words and the noise, ``preprocess.seeded_scalars`` for the five scalars."""
+        seed, sample_index = self._check_seed(seed, sample_index)
+        lib = _lib.load()
+        words = torch.empty((self.W, self.T, self.N), dtype=torch.int32, device=self.device)
+        noise = torch.empty((self.W, self.T * self.N, 3), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(lib.smos_train_prep_draws(seed, sample_index, self.N, float(self.aug.noise_mean), float(self.aug.noise_std),
+                                                 words.data_ptr(), noise.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
+                       "smos_train_prep_draws")
+        return preprocess.TrainDraws(words, noise, *preprocess.seeded_scalars(seed, sample_index, self.aug))
+
+    @staticmethod
+    def _check_seed(seed, sample_index):
+        seed, sample_index = int(seed), int(sample_index)
+        if not (0 <= seed < 2 ** 64 and 0 <= sample_index < 2 ** 64):
+            raise RuntimeError("DeviceTrainPreprocessor: seed and sample_index are unsigned 64-bit integers")
+        return seed, sample_index
+
+    # ---- building ---------------------------------------------------------------------------------------------------------
+    def build(self, scans, label_words, poses, draws=None, seed=None, sample_index=0, out=None, batch_slot=0, aligned=False):
+        """One sample.  scans: 5 [n_k, 4] float32 arrays in ``meta_list_raw`` order (numpy, uploaded through pinned staging, or
+        contiguous tensors already on the device); label_words: their [n_k] uint32 words (numpy uint32 / int32, or int32
+        device tensors); poses: 5 4x4 float64.  Exactly one of ``draws`` (explicit) and ``seed`` (with ``sample_index``).
+        ``out``: batch tensors as ``alloc_batch`` returns them (any batch stride; each sample slice contiguous): the sample is
+        written into slice ``batch_slot``; without ``out`` a batch of one is allocated.  Returns the dict of batch tensors.
+        aligned=True: the scans already went through the first alignment (the state in which the reference's copy-paste
+        augmentation edits them); only the windows' second alignment is applied.
+        Every argument is checked before the first launch; an argument error is a RuntimeError."""
+        lib = _lib.load()
+        if (draws is None) == (seed is None):
+            raise RuntimeError("DeviceTrainPreprocessor.build: give either draws or seed, not both and not neither")
+        if len(scans) != preprocess.TRAIN_FRAMES or len(label_words) != preprocess.TRAIN_FRAMES:
+            raise RuntimeError("DeviceTrainPreprocessor: a training sample has %d scans and label arrays, got %d and %d"
+                               % (preprocess.TRAIN_FRAMES, len(scans), len(label_words)))
+        if len(poses) != preprocess.TRAIN_FRAMES:
+            raise RuntimeError("DeviceTrainPreprocessor: a training sample has %d poses, got %d" % (preprocess.TRAIN_FRAMES, len(poses)))
+        for s, w in zip(scans, label_words):
+            if getattr(s, "ndim", None) != 2 or getattr(w, "ndim", None) != 1 or s.shape[0] != w.shape[0]:
+                raise RuntimeError("DeviceTrainPreprocessor: a scan [n, 4] needs n label words, got shapes %s and %s"
+                                   % (list(getattr(s, "shape", ())), list(getattr(w, "shape", ()))))
+        poses = [np.asarray(p, dtype=np.float64) for p in poses]
+        if any(p.shape != (4, 4) for p in poses):
+            raise RuntimeError("DeviceTrainPreprocessor: poses are 4x4 matrices")
+        N, W, T = self.N, self.W, self.T
+        if out is None:
+            out, batch_slot = self.alloc_batch(1), 0
+        slices = {}
+        for k, (shape, dtype) in self.output_shapes().items():
+            t = out.get(k)
+            if not (torch.is_tensor(t) and t.device == self.device and t.dtype == dtype and tuple(t.shape[1:]) == tuple(shape)
+                    and 0 <= batch_slot < t.shape[0] and t[batch_slot].is_contiguous()):
+                raise RuntimeError("DeviceTrainPreprocessor.build: out[%r] must be a %s tensor [B > %d, %s] on %s with contiguous "
+                                   "samples" % (k, dtype, batch_slot, ", ".join(str(d) for d in shape), self.device))
+            slices[k] = t[batch_slot]
+        self._check_rows(scans, "scans", (np.float32,), (torch.float32,), (4,))
+        self._check_rows(label_words, "label words", (np.uint32, np.int32), (torch.int32,), ())
+        if draws is not None:
+            self._check_draw(draws.words, "words", (W, T, N), np.uint32, (torch.int32,) + ((torch.uint32,) if hasattr(torch, "uint32") else ()))
+            self._check_draw(draws.noise, "noise", (W, T * N, 3), np.float64, (torch.float64,))
+        else:
+            seed, sample_index = self._check_seed(seed, sample_index)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            if draws is not None:
+                words = self._draw_tensor(draws.words, (W, T, N), torch.int32)
+                noise = self._draw_tensor(draws.noise, (W, T * N, 3), torch.float64)
+                words_ptr, noise_ptr, seed, sample_index = words.data_ptr(), noise.data_ptr(), 0, 0
+                shift, scale, h_flip, v_flip, theta_z = draws.shift, draws.scale, draws.h_flip, draws.v_flip, draws.theta_z
+            else:
+                words_ptr = noise_ptr = None
+                shift, scale, h_flip, v_flip, theta_z = preprocess.seeded_scalars(seed, sample_index, self.aug)
+            scan_ptrs, lengths, keep_s = self._device_rows(scans, torch.float32, (4,))
+            word_ptrs, _, keep_w = self._device_rows(label_words, torch.int32, ())
+            work_bytes = lib.smos_train_prep_work_bytes(max(lengths))
+            if work_bytes < 0:
+                raise RuntimeError("DeviceTrainPreprocessor: a scan of %d points is too large" % max(lengths))
+            work = self._work.get(stream.cuda_stream)
+            if work is None or work.numel() < work_bytes:
+                work = self._work[stream.cuda_stream] = torch.empty(work_bytes, dtype=torch.uint8, device=self.device)
+            inv0 = np.linalg.inv(poses[0])
+            first = np.stack([np.eye(4) if aligned else inv0.dot(p) for p in poses]).reshape(-1)
+            second = np.stack([np.linalg.inv(poses[w]).dot(poses[0]) for w in range(W)]).reshape(-1)
+            ang = float(theta_z) * np.pi / 180.0
+            vp5, vp3 = ctypes.c_void_p * preprocess.TRAIN_FRAMES, ctypes.c_void_p * W
+            targets = (ctypes.c_void_p * (len(self.target_names) * W))(
+                *[slices["%s_%d" % (name, w)].data_ptr() for name in self.target_names for w in range(W)])
+            _lib.check(lib.smos_train_prep_build(
+                vp5(*scan_ptrs), vp5(*word_ptrs), _lib.i64_array(lengths), _lib.f64_array(first), _lib.f64_array(second), self._range6,
+                self._bev3, self._rv4, N, words_ptr, noise_ptr, seed, sample_index, float(self.aug.noise_mean), float(self.aug.noise_std),
+                _lib.f64_array(shift), float(scale), int(v_flip), int(h_flip), float(np.cos(ang)), float(np.sin(ang)),
+                self._lut.data_ptr(), len(self.target_names), self._lut.shape[1],
+                vp3(*[slices["pcds_xyzi_%d" % w].data_ptr() for w in range(W)]),
+                vp3(*[slices["pcds_coord_%d" % w].data_ptr() for w in range(W)]),
+                vp3(*[slices["pcds_sphere_coord_%d" % w].data_ptr() for w in range(W)]), targets,
+                vp3(*[slices["pcds_bev_target_%d" % w].data_ptr() for w in range(W)]), slices["in_range_counts"].data_ptr(),
+                work.data_ptr(), work.numel(), stream.cuda_stream), "smos_train_prep_build")
+            for t in keep_s + keep_w + ([words, noise] if draws is not None else []):   # read by the launches above
+                t.record_stream(stream)
+        return out
+
+    def build_batch(self, samples, draws=None, seed=None, first_sample_index=0, out=None, aligned=False):
+        """samples: list of (scans, label_words, poses); draws: one ``TrainDraws`` per sample, or seed: sample b uses
+        ``sample_index = first_sample_index + b``.  Returns the dict ``AttNet.forward`` / ``StreamMOS_seg.AttNet.forward``
+        consume (keys ``pcds_xyzi_i``, ``pcds_coord_i``, ``pcds_sphere_coord_i``, one target per label map and
+        ``pcds_bev_target_i`` for i = 0..2, plus ``in_range_counts`` [B, 3, 3]), on the device, each sample written straight
+        into its slice."""
+        if (draws is None) == (seed is None):
+            raise RuntimeError("DeviceTrainPreprocessor.build_batch: give either draws or seed, not both and not neither")
+        if draws is not None and len(draws) != len(samples):
+            raise RuntimeError("DeviceTrainPreprocessor.build_batch: %d samples, %d draws" % (len(samples), len(draws)))
+        if out is None:
+            out = self.alloc_batch(len(samples))
+        for b, (scans, label_words, poses) in enumerate(samples):
+            self.build(scans, label_words, poses, draws=None if draws is None else draws[b], seed=seed,
+                       sample_index=first_sample_index + b, out=out, batch_slot=b, aligned=aligned)
+        return out
+
+    def check_counts(self, built):
+        """Raises if a frame of `built` had no point inside the range (synchronises the stream: the one host read)."""
+        check_train_counts(built["in_range_counts"].cpu().numpy())
