@@ -42,7 +42,7 @@ const char* smos_last_error(void);
 /* Test hook (process-wide, not part of the data path; the one piece of state the library keeps): caps the grid of the
  * persistent convolution kernels (smos_conv_cl / _rows_cl / _wino_cl / _wino1d_cl / _bf16_cl), of smos_stem_gemm, of
  * smos_pointnet_scatter / _rows / _rows_live, of smos_gather_scatter_cl / _live / _view and of the emit, copy, start and sum
- * kernels of smos_bilinear_gather_bwd_det / smos_msda_bwd_det and of smos_train_prep_build / _draws at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
+ * kernels of smos_bilinear_gather_bwd_det / smos_msda_bwd_det and of smos_train_prep_build / _draws and smos_copy_paste_* at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
  * item-boundary code paths, a wave's whole-tile / head / tail units of the stem, the scatter's software pipeline -- on shapes
  * small enough to check against float64.  The results do not depend on it. */
 int smos_debug_set_conv_grid_cap(int32_t blocks);
@@ -563,6 +563,45 @@ int smos_train_prep_build(const void* const* scans, const void* const* label_wor
  * (seed, sample_index) when it is given no draws. */
 int smos_train_prep_draws(uint64_t seed, uint64_t sample_index, int64_t N, double noise_mean, double noise_std,
                           uint32_t* words, double* noise, smos_stream_t stream);
+
+/*
+ * Copy-paste augmentation on the device (csrc/copy_paste.hip): SequenceCutPaste of the reference
+ * (datasets/copy_paste.py, copy_paste_seg.py) on the five scans of a training sample; host restatement:
+ * streammos_amd.preprocess.copy_paste_sample.  All pointers but the small host arrays named so are DEVICE pointers; everything
+ * runs on `stream`, nothing is read back.
+ *   state of a sample   frame k owns rows off_k .. off_k + n[k] + slots of four flat arrays, off_k = sum over the frames before
+ *                       it: pts [rows, 4] float32, words [rows] uint32, angles [rows, 2] float32 (phi, theta), flags [rows]
+ *                       uint8 (bit 0 alive, bit 1 object class).  A frame's rows are its scan points in their order, then one
+ *                       slot range per object in paste order (`slots` = the points of all objects).  A removed point and an
+ *                       unused slot hold the padding point (-1000, -1000, -4000, -1000); every row keeps its word.
+ *   status [count]      int32: the accepted trial of each object, -1 if none (or skipped)
+ * smos_copy_paste_begin: one launch.  scans[k] [n[k], 4] float32 raw, label_words[k] [n[k]] uint32, first_pose (HOST) five
+ * row-major 4x4 float64 inv(P_0) P_k: the first alignment (float64, rounded once), the angles, the flags, padded slots,
+ * status = -1.
+ * smos_copy_paste_object: four launches for object `number` (0-based, in paste order) of m >= 10 points (the caller skips
+ * smaller ones, copy_paste.py:195) whose slot range starts at row n[k] + slot of every frame.  scan0 / label_words0 /
+ * first_pose0: scan 0 again (the road points, semantic id 40, as form_seq takes them: never edited).  object_points [m, 4]
+ * float32 and footprint [4, 2] float64 (the x, y of the first four corners of the box scaled by 1.05) lie in the object bank.
+ * HOST arrays: shift_x5 / shift_y5 = velo_x * t * 0.1, velo_y * t * 0.1; order20 a permutation of 0..19 (trial j turns by
+ * 18 * order20[j] degrees on top of the trials before it); cos20 / sin20 of 18 i degrees.  noise [5, m, 3] float64 or NULL:
+ * generated in the kernels, Philox4x32-10 with key = seed and counter (point, 1 << 24 | call << 16 | number << 8 | frame,
+ * sample_index lo, hi), call 0 words 2, 3 -> x, call 1 words 0, 1 -> y and 2, 3 -> z through the float32 Box-Muller of
+ * smos_train_prep_build, times 0.001.  paste_word: the label word of the pasted points (label base + motion label).
+ * work: smos_copy_paste_work_bytes(n[0]) bytes of device scratch, 256-byte aligned (-1: bad size); a stream's objects share it.
+ * smos_copy_paste_draws: noise [5, m, 3] float64 exactly as the kernels generate it.
+ * Grids are capped by smos_debug_set_conv_grid_cap; the bits do not depend on the grid.
+ */
+int64_t smos_copy_paste_work_bytes(int64_t n0);
+int smos_copy_paste_begin(const void* const* scans, const void* const* label_words, const int64_t* n, const double* first_pose,
+                          int64_t slots, int32_t count, void* pts, void* words, void* angles, void* flags, int32_t* status,
+                          smos_stream_t stream);
+int smos_copy_paste_object(const void* scan0, const void* label_words0, const double* first_pose0, const int64_t* n, int64_t slots,
+                           void* pts, void* words, void* angles, void* flags, int32_t* status, int32_t count, int32_t number,
+                           const void* object_points, int32_t m, int64_t slot, const double* footprint, const double* shift_x5,
+                           const double* shift_y5, const uint8_t* order20, const double* cos20, const double* sin20,
+                           const double* noise, uint64_t seed, uint64_t sample_index, uint32_t paste_word, void* work,
+                           int64_t work_bytes, smos_stream_t stream);
+int smos_copy_paste_draws(uint64_t seed, uint64_t sample_index, int32_t number, int32_t m, double* noise, smos_stream_t stream);
 
 /* Multi-scale deformable attention, backward (training row f2).  Replaces
  * MultiScaleDeformableAttention.ms_deform_attn_backward (deformattn/src/cuda/ms_deform_attn_cuda.cu:83-153, kernels

@@ -92,6 +92,12 @@ SIGNATURES = {
                               ctypes.c_double, ctypes.c_double, vp, i32, i32, ctypes.POINTER(vp), ctypes.POINTER(vp),
                               ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, i64, vp],
     "smos_train_prep_draws": [ctypes.c_uint64, ctypes.c_uint64, i64, ctypes.c_double, ctypes.c_double, vp, vp, vp],
+    "smos_copy_paste_work_bytes": [i64],
+    "smos_copy_paste_begin": [ctypes.POINTER(vp), ctypes.POINTER(vp), c_i64p, c_f64p, i64, i32, vp, vp, vp, vp, vp, vp],
+    "smos_copy_paste_object": [vp, vp, c_f64p, c_i64p, i64, vp, vp, vp, vp, vp, i32, i32, vp, i32, i64, vp, c_f64p, c_f64p,
+                               ctypes.POINTER(ctypes.c_uint8), c_f64p, c_f64p, vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                               vp, i64, vp],
+    "smos_copy_paste_draws": [ctypes.c_uint64, ctypes.c_uint64, i32, i32, vp, vp],
     "smos_bias_act_cl": [vp, i64, vp, vp, i64, vp, i64, i64, i64, i32, vp],
     "smos_downsample_epilogue_cl": [vp, i64, vp, i64, vp, vp, i64, i64, i64, i64, i64, i32, vp],
     "smos_channel_gate_residual_cl": [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, vp],
@@ -145,6 +151,7 @@ def load():
     lib.smos_bilinear_gather_bwd_det_work_bytes.restype = ctypes.c_int64
     lib.smos_msda_bwd_det_work_bytes.restype = ctypes.c_int64
     lib.smos_train_prep_work_bytes.restype = ctypes.c_int64
+    lib.smos_copy_paste_work_bytes.restype = ctypes.c_int64
     lib.smos_conv_cl_sum_chunks.restype = ctypes.c_int64
     lib.smos_conv_wino_sum_chunks.restype = ctypes.c_int64
     lib.smos_basic_block_ws_floats.restype = ctypes.c_int64

@@ -6,9 +6,12 @@ point count, 4 test-time-augmentation flips, BEV / range-view quantisation and t
 feature.  All arithmetic is float32 exactly where the reference's numpy is float32, and float64 only in
 the pose transform (datasets/utils.py:116-126).
 
-Second half: the training sample of ``DataloadTrain.__getitem__`` (datasets/data_StreamMOS.py:292-364) without copy-paste,
-``build_train_sample``, with the random draws as an input, and the host restatement of the seeded draws the device builder
+Second half: the training sample of ``DataloadTrain.__getitem__`` (datasets/data_StreamMOS.py:292-364) behind its copy-paste
+step, ``build_train_sample``, with the random draws as an input, and the host restatement of the seeded draws the device builder
 (csrc/train_prep.hip) generates.  It is the host path: there is no C twin.
+
+Last part: that copy-paste step (``SequenceCutPaste``, datasets/copy_paste.py), ``copy_paste_sample``, again with explicit
+draws; the device stage is csrc/copy_paste.hip.
 """
 import numpy as np
 
@@ -309,7 +312,7 @@ def bev_label_grid(target, coord_xy, spec):
 
 
 def build_train_sample(scans, label_words, poses, frame_point_num, spec, aug, draws, label_maps=None, aligned=False):
-    """One training sample without copy-paste.  scans: 5 raw (n_k, 4) float32 scans in ``meta_list_raw`` order, label_words:
+    """One training sample (copy-paste, if any, has been applied before: ``copy_paste_sample``).  scans: 5 raw (n_k, 4) float32 scans in ``meta_list_raw`` order, label_words:
     their uint32 label words, poses: their 4x4 float64 poses, draws: TrainDraws.  label_maps: name -> LUT, one target per
     entry, the BEV label grid from the first (default: ``pcds_target`` through the SemanticKITTI learning map).
 
@@ -360,3 +363,282 @@ def build_train_sample(scans, label_words, poses, frame_point_num, spec, aug, dr
             if i == 0:
                 out["pcds_bev_target_%d" % w] = bev_label_grid(tgt, bev[0, :, :2, 0], spec)
     return out
+
+
+# ---- copy-paste augmentation (SequenceCutPaste, datasets/copy_paste.py; stage 2: datasets/copy_paste_seg.py) ------------------
+PASTE_TRIALS = 20                   # np.arange(0, 360, 18), shuffled (copy_paste.py:198-199)
+PASTE_STEP_DEG = 18
+PASTE_RAW_ID = 30                   # raw semantic id of a pasted point (copy_paste.py:236)
+PASTE_MIN_POINTS = 10               # copy_paste.py:195
+PASTE_MIN_ROAD = 5                  # more than this many road points under the box (copy_paste.py:209)
+PASTE_MAX_BLOCKERS = 3              # fewer than this many object-class points inside the view box (copy_paste.py:164)
+PASTE_NOISE_STD = 0.001             # copy_paste.py:140
+PASTE_BOX_SCALE = 1.05              # copy_paste.py:125
+PASTE_SPANS = (8.0, 1.0, 1.0)       # u, phi, theta (copy_paste.py:160)
+PASTE_ROAD_ID = 40                  # data_StreamMOS.py:231
+PASTE_MAX_OBJECTS = 20              # config/StreamMOS.py:34
+PASTE_CATEGORIES = ("other-vehicle", "truck", "car", "motorcyclist", "motorcycle", "person", "bicycle", "bicyclist")
+PASTE_VELOCITY = {"other-vehicle": (-15, 15), "truck": (-15, 15), "car": (-15, 15), "motorcyclist": (-8, 8), "motorcycle": (-8, 8),
+                  "person": (-3, 3), "bicycle": (-8, 8), "bicyclist": (-8, 8)}
+PASTE_PAD = (PAD_XYZI, PAD_XYZI, PAD_Z, PAD_XYZI)
+
+
+class PasteObject:
+    """One entry of the object bank: ``pcds`` float32 [m, 4], box ``center`` [3], ``size`` [3] and ``yaw`` as float64 (a file
+    that stores them narrower is widened first: the box is float64 arithmetic from there on), ``cate`` one of PASTE_CATEGORIES."""
+
+    def __init__(self, pcds, center, size, yaw, cate):
+        self.pcds = np.ascontiguousarray(pcds, dtype=np.float32)
+        self.center = np.asarray(center, dtype=np.float64).reshape(3)
+        self.size = np.asarray(size, dtype=np.float64).reshape(3)
+        self.yaw = float(np.asarray(yaw, dtype=np.float64).reshape(()))
+        self.cate = str(cate)
+        if self.pcds.ndim != 2 or self.pcds.shape[1] != 4:
+            raise ValueError("an object's pcds are [m, 4] float32, got %s" % (list(self.pcds.shape),))
+        if self.cate not in PASTE_CATEGORIES:
+            raise ValueError("unknown object category %r" % (self.cate,))
+
+
+class PasteDraws:
+    """The random draws of one sample's copy-paste: ``count`` objects; per object the bank ``index``, the signed ``velocity``
+    (m/s), the trial ``order`` (uint8 [count, 20], each row a permutation of 0..19: trial j rotates by 18 * order[j] degrees) and
+    the ``noise`` (float64 [5, m, 3] per object, or None: generated in the kernels from (seed, sample index))."""
+
+    def __init__(self, index, velocity, order, noise=None):
+        self.index = [int(i) for i in index]
+        self.count = len(self.index)
+        self.velocity = [float(v) for v in velocity]
+        self.order = np.asarray(order, dtype=np.uint8).reshape(self.count, PASTE_TRIALS)
+        self.noise = None if noise is None else list(noise)
+
+
+def paste_label_maps(label_maps, paste_labels):
+    """Label maps extended for pasted points: every LUT is zero-filled to the longest one's length (the *label base*), then gets
+    the three labels of a pasted point's word label_base + motion label (motion 0 / 1 / 2).  paste_labels: name -> 3 labels,
+    e.g. {"pcds_target": (0, 1, 2), "pcds_bf_target": (2, 2, 2)} (copy_paste.py:235, copy_paste_seg.py:237).  Returns
+    (maps, label_base)."""
+    base = max(int(np.asarray(m).shape[0]) for m in label_maps.values())
+    if set(paste_labels) != set(label_maps):
+        raise ValueError("paste_labels names %s, the label maps %s" % (sorted(paste_labels), sorted(label_maps)))
+    out = {}
+    for name, lut in label_maps.items():
+        ext = np.zeros(base + 3, dtype=np.asarray(lut).dtype)
+        ext[:np.asarray(lut).shape[0]] = np.asarray(lut)
+        ext[base:] = np.asarray(paste_labels[name]).reshape(3)
+        out[name] = ext
+    return out, base
+
+
+def paste_motion_label(velocity):
+    """copy_paste.py:187-193 on |v|."""
+    v = abs(float(velocity))
+    return 2 if v >= 1 else (1 if v < 0.3 else 0)
+
+
+def paste_rotations():
+    """cos and sin of the 20 trial angles as cv2.getRotationMatrix2D takes them (alpha = cos, beta = sin of angle * pi / 180)."""
+    a = np.arange(PASTE_TRIALS, dtype=np.float64) * PASTE_STEP_DEG * np.pi / 180.0
+    return np.cos(a), np.sin(a)
+
+
+def paste_box_footprint(obj):
+    """compute_box_3d (copy_paste.py:21-43) of the box scaled by 1.05: its first four corners' x, y (the quadrilateral the road
+    test uses), float64 [4, 2]."""
+    size = obj.size * PASTE_BOX_SCALE
+    c, s = np.cos(obj.yaw), np.sin(obj.yaw)
+    xc = np.array([size[0] / 2, size[0] / 2, -size[0] / 2, -size[0] / 2])
+    yc = np.array([size[1] / 2, -size[1] / 2, -size[1] / 2, size[1] / 2])
+    return np.stack((c * xc - s * yc + obj.center[0], s * xc + c * yc + obj.center[1]), axis=1)
+
+
+def paste_velocity_xy(obj, velocity):
+    return -1 * velocity * np.sin(obj.yaw), velocity * np.cos(obj.yaw)
+
+
+def view_angles(x, y, z):
+    """get_fov / occlusion_process (copy_paste.py:93-115) in float32: u, phi = arctan2(x, y), theta = arcsin(z / d)."""
+    f = np.float32
+    x, y, z = x.astype(f), y.astype(f), z.astype(f)
+    d = np.sqrt(x * x + y * y + z * z) + f(1e-12)
+    u = np.sqrt(x * x + y * y) + f(1e-12)
+    return u, np.arctan2(x, y), np.arcsin(z / d)
+
+
+def inside_quad(p, quad):
+    """in_hull of a convex quadrilateral whose corners are given in order: p [n, 2] -> (inside [n], distance to the boundary
+    [n]); the sign of the four edge cross products decides, in float64."""
+    p = np.asarray(p, dtype=np.float64)
+    a, b = quad, np.roll(quad, -1, axis=0)
+    e = b - a
+    rel = p[:, None, :] - a[None, :, :]
+    cross = e[None, :, 0] * rel[..., 1] - e[None, :, 1] * rel[..., 0]
+    inside = (cross >= 0).all(axis=1) | (cross <= 0).all(axis=1)
+    along = np.clip((rel * e[None]).sum(axis=2) / (e * e).sum(axis=1)[None, :], 0.0, 1.0)
+    gap = rel - along[..., None] * e[None]
+    return inside, np.sqrt((gap * gap).sum(axis=2)).min(axis=1)
+
+
+def seeded_paste_scalars(seed, sample_index, bank_categories, max_objects=PASTE_MAX_OBJECTS):
+    """The host side of seeded copy-paste draws: ``random.Random`` keyed on (seed, sample index) like ``seeded_scalars`` (under a
+    tag of its own, so the two streams differ), drawn in the reference's order: the count, then per object category, file,
+    velocity and the trial order.  bank_categories: per category the list of bank indices.  Returns (index, velocity, order)."""
+    import random
+    rng = random.Random((1 << 128) | (int(seed) << 64) | int(sample_index))
+    count = rng.randint(0, int(max_objects))
+    index, velocity, order = [], [], []
+    filled = [c for c in range(len(PASTE_CATEGORIES)) if len(bank_categories[c]) > 0]
+    for _ in range(count):
+        c = filled[rng.randrange(len(filled))]
+        index.append(int(bank_categories[c][rng.randrange(len(bank_categories[c]))]))
+        lo, hi = PASTE_VELOCITY[PASTE_CATEGORIES[c]]
+        velocity.append(lo + (hi - lo) * rng.random())
+        perm = list(range(PASTE_TRIALS))
+        rng.shuffle(perm)
+        order.append(perm)
+    return index, velocity, np.asarray(order, dtype=np.uint8).reshape(count, PASTE_TRIALS)
+
+
+def seeded_paste_noise(seed, sample_index, obj, m):
+    """Host restatement of the kernels' seeded noise of object number `obj` with m points: float64 [5, m, 3] (Philox counter
+    layout: include/smos.h).  numpy's float32 log / cos may differ from the device's in the last bits."""
+    f = np.float32
+    t, p = np.meshgrid(np.arange(TRAIN_FRAMES, dtype=np.uint64), np.arange(int(m), dtype=np.uint64), indexing="ij")
+    key = np.array([int(seed) & _M32, (int(seed) >> 32) & _M32], dtype=np.uint64)
+    w = []
+    for call in (0, 1):
+        c1 = np.uint64(1 << 24) | (np.uint64(call) << np.uint64(16)) | (np.uint64(int(obj)) << np.uint64(8)) | t
+        ctr = np.stack((p, c1, np.full_like(p, int(sample_index) & _M32), np.full_like(p, (int(sample_index) >> 32) & _M32)), axis=-1)
+        w.append(philox4x32(ctr, key))
+    z = np.stack((box_muller_f32(w[0][..., 2], w[0][..., 3]), box_muller_f32(w[1][..., 0], w[1][..., 1]),
+                  box_muller_f32(w[1][..., 2], w[1][..., 3])), axis=-1)
+    return (z * f(PASTE_NOISE_STD) + f(0.0)).astype(np.float64)
+
+
+PASTE_VARIANTS = ("non_accumulating_rotation", "road_refreshed", "road_ge_5", "closed_upper_bound", "any_frame",
+                  "pasted_not_object_class")
+
+
+def copy_paste_sample(scans_aligned, label_words, road_points, objects, draws, label_base=360, variant=None, trace=None):
+    """SequenceCutPaste.__call__ with explicit draws, on scans that went through the first alignment.
+
+    scans_aligned: 5 float32 [n_k, 4]; label_words: their uint32 words; road_points: scan 0's points with semantic id 40 as
+    form_seq takes them (before any paste, never updated); objects: the bank (list of PasteObject); draws: PasteDraws with noise.
+    Returns (scans', words', status): frame k has n_k + sum(m_i) rows, the originals in their order, then one slot range per
+    object in paste order.  A removed point, and the slot of an object that was skipped (fewer than 10 points) or found no valid
+    trial, holds the validation padding point; every row keeps its word.  A pasted point's word is label_base + its motion label
+    (0 / 1 / 2).  status [count] int32: the accepted trial, or -1.
+
+    Types follow the reference under numpy's current promotion rules: the per-frame shift and the noise are float64 sums rounded
+    once to float32, every rotation is a float64 product rounded to float32 (so the rotations accumulate their roundings), the
+    road lift and the view angles are float32, the box footprint stays float64.  variant: one deliberate error (tests only).
+    trace: a list that receives one dict per trial (road count, edge distances, spans, boxes, counts)."""
+    f, d = np.float32, np.float64
+    if variant is not None and variant not in PASTE_VARIANTS:
+        raise ValueError("unknown variant %r" % (variant,))
+    if len(scans_aligned) != TRAIN_FRAMES or len(label_words) != TRAIN_FRAMES:
+        raise ValueError("copy-paste edits the %d scans of a training sample" % TRAIN_FRAMES)
+    sizes = [objects[i].pcds.shape[0] for i in draws.index]
+    total = int(sum(sizes))
+    n = [int(s.shape[0]) for s in scans_aligned]
+    pts, words, raw, alive, phi, theta = [], [], [], [], [], []
+    for k in range(TRAIN_FRAMES):
+        p = np.empty((n[k] + total, 4), dtype=f)
+        p[:] = np.array(PASTE_PAD, dtype=f)
+        p[:n[k]] = scans_aligned[k]
+        w = np.zeros(n[k] + total, dtype=np.uint32)
+        w[:n[k]] = np.asarray(label_words[k]).astype(np.uint32)
+        pts.append(p)
+        words.append(w)
+        raw.append((w & np.uint32(0xFFFF)).astype(np.int64))
+        alive.append(np.arange(n[k] + total) < n[k])
+        _, ph, th = view_angles(p[:, 0], p[:, 1], p[:, 2])
+        phi.append(ph)
+        theta.append(th)
+    road = np.asarray(road_points, dtype=f)
+    rot_c, rot_s = paste_rotations()
+    status = np.full(draws.count, -1, dtype=np.int32)
+    upper = (lambda v, hi: v <= hi) if variant == "closed_upper_bound" else (lambda v, hi: v < hi)
+    slot = 0
+    for i in range(draws.count):
+        obj, m = objects[draws.index[i]], sizes[i]
+        at, slot = slot, slot + m
+        if m < PASTE_MIN_POINTS:
+            continue
+        v = draws.velocity[i]
+        noise = np.asarray(draws.noise[i], dtype=d)
+        if noise.shape != (TRAIN_FRAMES, m, 3):
+            raise ValueError("object %d: noise of shape %s, expected %s" % (i, list(noise.shape), [TRAIN_FRAMES, m, 3]))
+        vx, vy = paste_velocity_xy(obj, v)
+        frames = []
+        for t in range(TRAIN_FRAMES):
+            p = obj.pcds.copy()
+            p[:, 0] = (p[:, 0].astype(d) - vx * t * 0.1).astype(f)
+            p[:, 1] = (p[:, 1].astype(d) - vy * t * 0.1).astype(f)
+            p[:, :3] = (p[:, :3].astype(d) + noise[t]).astype(f)
+            frames.append(p)
+        quad = paste_box_footprint(obj)                  # frame 0: t * 0.1 = 0, the footprint of the road test
+        start = ([p.copy() for p in frames], quad.copy())
+        motion = paste_motion_label(v)
+        for j in range(PASTE_TRIALS):
+            c, s = rot_c[draws.order[i, j]], rot_s[draws.order[i, j]]
+            if variant == "non_accumulating_rotation":
+                for t in range(TRAIN_FRAMES):
+                    frames[t][:, :2] = start[0][t][:, :2]
+                quad = start[1].copy()
+            for p in frames:
+                x, y = p[:, 0].astype(d), p[:, 1].astype(d)
+                p[:, 0], p[:, 1] = (x * c + y * s).astype(f), (y * c - x * s).astype(f)
+            quad = np.stack((quad[:, 0] * c + quad[:, 1] * s, quad[:, 1] * c - quad[:, 0] * s), axis=1)
+            if variant == "road_refreshed":
+                road = pts[0][alive[0] & ((raw[0] == PASTE_ROAD_ID) | (raw[0] == PASTE_RAW_ID))]
+            under, edge = inside_quad(road[:, :2], quad)
+            n_road = int(under.sum())
+            rec = {"object": i, "trial": j, "road_count": n_road, "road_edge": float(edge.min()) if edge.size else np.inf}
+            if trace is not None:
+                trace.append(rec)
+            if not (n_road >= PASTE_MIN_ROAD if variant == "road_ge_5" else n_road > PASTE_MIN_ROAD):
+                continue
+            road_mean = f(road[under][:, 2].mean())
+            for p in frames:
+                p[:, 2] = p[:, 2] + (road_mean - p[:, 2].min())
+            ok, masks = [], []
+            rec["frames"] = []
+            for t in range(TRAIN_FRAMES):
+                u, ph, th = view_angles(frames[t][:, 0], frames[t][:, 1], frames[t][:, 2])
+                spans = (abs(u.max() - u.min()), abs(ph.max() - ph.min()), abs(th.max() - th.min()))
+                fits = spans[0] < PASTE_SPANS[0] and spans[1] < PASTE_SPANS[1] and spans[2] < PASTE_SPANS[2]
+                fr = {"spans": tuple(float(v_) for v_ in spans), "fits": bool(fits)}
+                rec["frames"].append(fr)
+                if not fits:
+                    ok.append(False)
+                    masks.append(None)
+                    continue
+                box = (ph.min(), ph.max(), th.min(), th.max())
+                mask = alive[t] & (phi[t] >= box[0]) & upper(phi[t], box[1]) & (theta[t] >= box[2]) & upper(theta[t], box[3])
+                cls = ((raw[t] >= 10) & (raw[t] < 33)) | ((raw[t] >= 252) & (raw[t] < 260))
+                if variant == "pasted_not_object_class":
+                    cls = cls & (np.arange(cls.shape[0]) < n[t])
+                blockers = int((mask & cls).sum())
+                if trace is not None:
+                    e = 1e-4
+                    wide = alive[t] & (phi[t] >= box[0] - e) & (phi[t] <= box[1] + e) & (theta[t] >= box[2] - e) & (theta[t] <= box[3] + e)
+                    deep = alive[t] & (phi[t] >= box[0] + e) & (phi[t] < box[1] - e) & (theta[t] >= box[2] + e) & (theta[t] < box[3] - e)
+                    fr.update(box=tuple(float(b) for b in box), blockers=blockers, removed=int(mask.sum()),
+                              removed_pasted=int((mask & (np.arange(mask.shape[0]) >= n[t])).sum()), near=np.nonzero(wide & ~deep)[0])
+                ok.append(blockers < PASTE_MAX_BLOCKERS)
+                masks.append(mask)
+            rec["valid"] = ok
+            if not (any(ok) and all(mk is not None for mk in masks) if variant == "any_frame" else all(ok)):
+                continue
+            for t in range(TRAIN_FRAMES):
+                pts[t][masks[t]] = np.array(PASTE_PAD, dtype=f)
+                alive[t][masks[t]] = False
+                rows = slice(n[t] + at, n[t] + at + m)
+                pts[t][rows] = frames[t]
+                words[t][rows] = np.uint32(label_base + motion)
+                raw[t][rows] = PASTE_RAW_ID
+                alive[t][rows] = True
+                _, phi[t][rows], theta[t][rows] = view_angles(frames[t][:, 0], frames[t][:, 1], frames[t][:, 2])
+            status[i] = j
+            break
+    return pts, words, status
