@@ -385,7 +385,7 @@ class InferenceEngine:
         (block, HIP stream, scratch namespace): blocks of different pipeline stages run concurrently on different streams, the same
         block may run on two streams at once (encode(t) on the main stream next to encode(t+1) on the side stream), and
         hipGraphs captured from one engine for several TTA groups replay concurrently with the addresses baked in
-        (namespace = group index, ops.set_workspace_namespace in StreamRunner._capture) -- a shared scratch would be a data
+        (namespace = group index, ops.set_workspace_namespace in StreamRunner._capture_groups) -- a shared scratch would be a data
         race in each case."""
         table = p.scratch
         if table is None:

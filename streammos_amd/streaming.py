@@ -64,19 +64,24 @@ class VoxelVoter:
         self.frames.clear()
         self.next_id = 0
 
-    def _vote(self, fid):
+    def _window(self, fid):
+        """(history, window) of a frame: history = [(frame id, its pose in the frame's coordinates)] for the resident frames
+        that vote with it, window = their (points, preds, pose difference) followed by the frame itself."""
         pts, pred, pose = self.frames[fid]
         inv_cur = np.linalg.inv(pose)
+        history = [(h, inv_cur.dot(self.frames[h][2])) for h in vote_history_ids(fid, self.window) if h in self.frames]
+        window = [(self.frames[h][0], self.frames[h][1], diff) for h, diff in history] + [(pts, pred, None)]
+        return history, window
+
+    def _resolve(self, fid, window, lut):
+        """clear / accumulate / resolve: the voxel vote of the frame's points over `window`, through `lut` when given."""
+        pts, pred, _ = self.frames[fid]
         ops.vote_clear(self.table)
-        window = []
-        for h in vote_history_ids(fid, self.window):
-            if h not in self.frames:
-                continue
-            hp, hl, hpose = self.frames[h]
-            window.append((hp, hl, inv_cur.dot(hpose)))
-        window.append((pts, pred, None))
         ops.vote_accumulate_frames(window, self.table, recip_quantize=self.recip)     # one launch for the whole window
-        return ops.vote_resolve(pts, pred, self.table, lut=self.lut, recip_quantize=self.recip)
+        return ops.vote_resolve(pts, pred, self.table, lut=lut, recip_quantize=self.recip)
+
+    def _vote(self, fid):
+        return self._resolve(fid, self._window(fid)[1], self.lut)
 
     def push(self, points, preds, pose):
         fid = self.next_id
@@ -204,13 +209,9 @@ class InstanceVoter(VoxelVoter):
         ops.instance_apply(out["names"], out["slot_of"], buf["counts"], buf["k"], labels)
 
     def _vote(self, fid):
-        pts, pred, pose = self.frames[fid]
-        inv_cur = np.linalg.inv(pose)
-        history = [(h, inv_cur.dot(self.frames[h][2])) for h in vote_history_ids(fid, self.window) if h in self.frames]
-        window = [(self.frames[h][0], self.frames[h][1], diff) for h, diff in history] + [(pts, pred, None)]
-        ops.vote_clear(self.table)
-        ops.vote_accumulate_frames(window, self.table, recip_quantize=self.recip)
-        labels = ops.vote_resolve(pts, pred, self.table, lut=None, recip_quantize=self.recip)
+        pts, pred, _ = self.frames[fid]
+        history, window = self._window(fid)
+        labels = self._resolve(fid, window, None)       # class ids: the LUT comes after the instance vote
         if self.device_resident:
             self._vote_device(fid, window, labels)
             return self.lut[labels.long()] if self.lut is not None else labels
@@ -280,7 +281,138 @@ def set_conv_precision(model, conv_precision):
     model.engine_conv_precision = conv_precision
 
 
-class StreamRunner:
+_KEYS = ("pcds_xyzi", "pcds_coord", "pcds_sphere_coord")      # the network's three input tensors
+
+
+def raw_labels(labels, dev, pre=None):
+    """labels [N] uint8 of the padded sample `dev` (from the DevicePreprocessor `pre` or from StreamRunner.upload) -> [n_raw]
+    uint8 for the raw scan, 0 where a point was out of range (val_StreamMOS.py:112-118); None for inputs without a way back."""
+    if "prefix" in dev:
+        return pre.unpad_labels(labels, dev)
+    if "valid_index" in dev:
+        raw = torch.zeros(dev["n_raw"], dtype=torch.uint8, device=labels.device)
+        raw.index_copy_(0, dev["valid_index"], labels[:dev["n_valid"]])
+        return raw
+    return None
+
+
+class _TwoStreamRunner:
+    """What both runners share: how frame t+1 is issued beside frame t.  Only the temporal fusion needs the previous frame, so
+    with pipeline=True the encoder of frame t+1 (point MLP, scatters, the BEV / range-view stages: ~60 % of the work) runs on a
+    second HIP stream while frame t is decoded on the main one.  (Putting the serial [third BEV stage -> temporal fusion] chain
+    on a third stream of its own was measured too: 144 vs 146 scans/s, so the simpler two-stream schedule stays.)
+    pipeline=False is the same step on one stream: no side stream is probed, the next frame's inputs are ignored."""
+
+    def __init__(self, model, device, conv_precision, pipeline, skip_padding):
+        self.device = torch.device(device)
+        self.model = model.to(self.device).eval()
+        set_conv_precision(self.model, conv_precision)
+        self.pipeline = pipeline
+        self.skip_padding = bool(skip_padding)      # hand the inputs' device-side count of real points to encode and decode
+        self._side = concurrent_stream(self.device) if pipeline else None
+        self._pending = None                # (inputs, their encoder's output) issued on the side stream by the previous step
+
+    def reset(self):
+        """A new sequence: no recurrent memory, frame 0, and the encoder issued ahead is dropped."""
+        self.memory, self.frame, self._pending = None, 0, None
+
+    def _encode(self, eng, dev):
+        return eng.encode(*(dev[k] for k in _KEYS), n_live=dev.get("n_live") if self.skip_padding else None)
+
+    def _encode_decode(self, dev, next_dev):
+        """encode (unless `dev` is the very object the previous step encoded ahead) and decode `dev`; beside the decode, the
+        encoder of `next_dev` on the side stream.  The engine's result tuple, or None when the model has no fused engine
+        for these inputs and nothing runs ahead (the caller falls back to model.infer)."""
+        eng = self.model._engine_for(dev["pcds_xyzi"])
+        if eng is None:
+            if self._side is None:
+                return None
+            raise RuntimeError("%s(pipeline=True) needs the fused GPU engine (eval mode, fast_inference)" % type(self).__name__)
+        main = torch.cuda.current_stream(self.device)
+        pending, self._pending = self._pending, None
+        if pending is not None and pending[0] is dev:
+            enc = pending[1]
+            main.wait_stream(self._side)                # encoder of this frame, issued during the previous step
+        else:
+            enc = self._encode(eng, dev)
+        if next_dev is not None and self._side is not None:     # encoder of the NEXT frame, concurrent with this decode
+            # the side stream must start behind the producers of next_dev.  Inputs made by upload() carry the event
+            # recorded behind their H2D copies; anything else (e.g. device preprocessing on main) is ordered behind
+            # main's whole tail.  Two encodes of one engine may run concurrently (frame 0: encode(t) on main beside
+            # encode(t+1) here): every piece of engine scratch is keyed by stream (engine._block_ws, ops._stream_workspace).
+            ready = next_dev.get("ready")
+            if ready is not None:
+                self._side.wait_event(ready)
+            else:
+                self._side.wait_stream(main)
+            with torch.cuda.stream(self._side):
+                nxt = self._encode(eng, next_dev)
+            for t in list(nxt.values()) + [next_dev[k] for k in _KEYS]:
+                if torch.is_tensor(t):
+                    t.record_stream(main)
+                    t.record_stream(self._side)
+            self._pending = (next_dev, nxt)
+        return eng.decode(enc, self.memory if self.frame > 0 else None, want_aux=False,       # the runners use pred_cls only
+                          n_live=dev.get("n_live") if self.skip_padding else None)
+
+
+class ScanUploads:
+    """Host scan -> device, once per scan object (a window re-uses the scans of the previous frames), through a small
+    ring of pinned staging buffers: a copy from pageable memory would hold the host until the stream has drained, and
+    pinning per call costs milliseconds."""
+
+    SLOTS, SLOT_FLOATS, CACHED = 8, 4 * 160000, 16
+
+    def __init__(self, device):
+        self.device = device
+        self.cache = collections.OrderedDict()      # id(scan) -> (scan, device copy, event behind the copy, its stream)
+        self.slots = []                             # [pinned buffer, event of the copy that last read it]
+        self.next = 0
+
+    def reset(self):
+        """Forgets the uploaded scans; the pinned ring stays (StreamRunner.close drops it with the whole object)."""
+        self.cache.clear()
+
+    def upload(self, scan):
+        """The scan on the device, valid on the CURRENT stream."""
+        cur = torch.cuda.current_stream(self.device)
+        hit = self.cache.get(id(scan))
+        if hit is not None and hit[0] is scan:
+            # the copy may still be in flight on ANOTHER stream (the window of frame t is uploaded on main, the look-ahead
+            # window of frame t+1 re-uses two of its scans on the side stream, and the other way round when the look-ahead
+            # misses): order this stream behind the copy and tell the allocator about the second user
+            _, dev, done, owner = hit
+            if owner != cur.cuda_stream:
+                cur.wait_event(done)
+                dev.record_stream(cur)
+            return dev
+        host = scan if torch.is_tensor(scan) else torch.from_numpy(np.ascontiguousarray(scan, dtype=np.float32))
+        if host.is_cuda:
+            return host
+        done = torch.cuda.Event()
+        if not host.is_pinned():
+            if len(self.slots) < self.SLOTS:
+                self.slots.append([torch.empty(max(host.numel(), self.SLOT_FLOATS), dtype=torch.float32).pin_memory(), None])
+                slot = self.slots[-1]
+            else:
+                slot = self.slots[self.next % self.SLOTS]
+                self.next += 1
+            if slot[1] is not None:
+                slot[1].synchronize()                       # the copy that last used this buffer (8 uploads ago)
+            if slot[0].numel() < host.numel():
+                slot[0] = torch.empty(host.numel(), dtype=torch.float32).pin_memory()
+            staged = slot[0][:host.numel()].view(host.shape)
+            staged.copy_(host)
+            host, slot[1] = staged, done
+        dev = host.to(self.device, non_blocking=True)
+        done.record(cur)
+        self.cache[id(scan)] = (scan, dev, done, cur.cuda_stream)
+        while len(self.cache) > self.CACHED:
+            self.cache.popitem(last=False)
+        return dev
+
+
+class StreamRunner(_TwoStreamRunner):
     """infer -> TTA reduce -> labels for the raw scan -> voxel voting, all on one device, one stream."""
 
     def __init__(self, model, device="cuda:0", vote=True, recip_quantize=False, graph=False, split=1, pipeline=False,
@@ -293,9 +425,12 @@ class StreamRunner:
         conv_precision "fp32" / "bf16": sets model.engine_conv_precision (None: the model's setting, "fp32" by default).
         instance_device (vote="instance"): the voter's device-resident path, InstanceVoter(device_resident=True); None reads
         the A/B switch SMOS_INSTANCE_DEVICE (0 when unset)."""
-        self.device = torch.device(device)
-        self.model = model.to(self.device).eval()
-        set_conv_precision(self.model, conv_precision)
+        # skip_padding: the reference pads every scan to frame_point_num with points at -1000 (datasets/data_StreamMOS.py:568-571)
+        # and cuts their predictions off again (val_StreamMOS.py:113).  The runner tells the point head how many points are
+        # real (a device-side count: no host sync); the padding tail's logits come back as zeros instead of being computed
+        # (25 % of the points of a SemanticKITTI scan at frame_point_num = 160 000, 40 % of the bench's synthetic ones).
+        # Labels, raw labels and votes of every real point are unchanged; AttNet.infer (the reference API) computes all N.
+        super().__init__(model, device, conv_precision, pipeline, skip_padding)
         # vote: False / True (voxel voting) / "instance" (voxel + instance voting; needs the StreamMOS_seg model)
         if vote == "instance":
             if instance_device is None:
@@ -305,30 +440,18 @@ class StreamRunner:
             self.voter = VoxelVoter(self.device, recip_quantize=recip_quantize) if vote else None
         self.use_graph = graph
         self.split = max(1, int(split))
-        self._graphs = None
+        self._graphs = self._groups = self._g_shape = self._g_pred = self._g_engine = None      # set by _capture
         self._ws_owner = ops.new_workspace_owner()      # names this runner's scratch namespaces (never reused, unlike id())
-        # pipeline=True: only the temporal fusion needs the previous frame, so the encoder of frame t+1 (point MLP,
-        # scatters, the BEV / range-view stages: ~60 % of the work) is issued on a second HIP stream while frame t
-        # is decoded on the main one.  step() must then be given the next frame's inputs (one frame of look-ahead).
-        self.pipeline = pipeline
-        # skip_padding: the reference pads every scan to frame_point_num with points at -1000 (datasets/data_StreamMOS.py:568-571)
-        # and cuts their predictions off again (val_StreamMOS.py:113).  The runner tells the point head how many points are
-        # real (a device-side count: no host sync); the padding tail's logits come back as zeros instead of being computed
-        # (25 % of the points of a SemanticKITTI scan at frame_point_num = 160 000, 40 % of the bench's synthetic ones).
-        # Labels, raw labels and votes of every real point are unchanged; AttNet.infer (the reference API) computes all N.
-        self.skip_padding = bool(skip_padding)
-        self._side = concurrent_stream(self.device) if pipeline else None
-        self._pre_enc = None
-        self.reset()
+        self._pre = None                # step_raw: the DevicePreprocessor of the frame_point_num in use
+        self._uploads = ScanUploads(self.device)
+        self._raw_ahead = None          # step_raw: (current scan of the window prepared ahead, its inputs)
+        self._last_built = None         # the inputs of the last step_raw
+        self.reset()                    # memory, frame: the state of a sequence
 
     # ---- hipGraph capture -------------------------------------------------------------------
-    _KEYS = ("pcds_xyzi", "pcds_coord", "pcds_sphere_coord")
-
     def _capture(self, dev):
         # The channels-last engine is captured as it stands: every convolution is the library's own kernel
-        # (csrc/conv_igemm.hip), so no MIOpen solver is replayed.  (Round 1 pinned the NCHW engine here because MIOpen's
-        # composable-kernel grouped-conv solvers gave ~2 % wrong logits under replay; the cause was never established and
-        # those solvers are no longer on the path.)
+        # (csrc/conv_igemm.hip), so no MIOpen solver is replayed.
         with torch.no_grad():
             eng = self.model._engine_for(dev["pcds_xyzi"])
         if eng is None:
@@ -352,8 +475,8 @@ class StreamRunner:
         for gi in range(k):
             sl = slice(gi * per, (gi + 1) * per)
             ops.set_workspace_namespace(("graph", self._ws_owner, gi))    # per-group scratch: the groups' graphs replay concurrently
-            g_in = {key: dev[key][sl].clone() for key in self._KEYS}
-            batch = {key: g_in[key].unsqueeze(0) for key in self._KEYS}
+            g_in = {key: dev[key][sl].clone() for key in _KEYS}
+            batch = {key: g_in[key].unsqueeze(0) for key in _KEYS}
             side.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(side), torch.no_grad():
                 # eager warm-up on a side stream: MIOpen algorithm search, lazy engine build, allocator pools
@@ -380,7 +503,7 @@ class StreamRunner:
         main = torch.cuda.current_stream(self.device)
         first = self.frame == 0
         for grp in self._groups:
-            for key in self._KEYS:
+            for key in _KEYS:
                 grp["in"][key].copy_(dev[key][grp["slice"]])
         for grp in self._groups:
             grp["stream"].wait_stream(main)
@@ -393,17 +516,20 @@ class StreamRunner:
         return self._g_pred
 
     def reset(self):
-        self.memory = None
-        self.frame = 0
-        self._pre_enc = None
+        """A new sequence: additionally the voting window starts over and the step_raw window prepared ahead and the cache of
+        uploaded scans are dropped.  Engine, captured graphs, preprocessor and the pinned staging ring stay warm."""
+        super().reset()
         self._raw_ahead = None
-        self.__dict__.pop("_raw_cache", None)
+        self._uploads.reset()
         if self.voter is not None:
             self.voter.reset()
 
     def close(self):
         """Frees the per-stream scratch this runner's HIP streams hold (ops._stream_workspace: ~1.2 GB per stream at the
-        validation shape).  The runner stays usable; the scratch is re-allocated on the next frame."""
+        validation shape), the look-ahead, the cache of uploaded scans and the pinned staging ring.  The runner stays usable
+        and keeps its place in the sequence; all of it is re-allocated on the next frame."""
+        self._pending = self._raw_ahead = None
+        self._uploads = ScanUploads(self.device)
         main = torch.cuda.current_stream(self.device).cuda_stream
         ops.release_stream_workspaces(self.device, main)
         if self._side is not None:
@@ -414,8 +540,7 @@ class StreamRunner:
 
     def upload(self, sample, raw_scan=None):
         """Host sample (streammos_amd.preprocess.build_sample) -> device-resident inputs."""
-        dev = {k: torch.from_numpy(np.ascontiguousarray(sample[k])).to(self.device)
-               for k in ("pcds_xyzi", "pcds_coord", "pcds_sphere_coord")}
+        dev = {k: torch.from_numpy(np.ascontiguousarray(sample[k])).to(self.device) for k in _KEYS}
         dev["valid_index"] = torch.from_numpy(np.nonzero(sample["valid_mask"])[0]).to(self.device)
         dev["n_raw"] = int(sample["valid_mask"].shape[0])
         dev["n_valid"] = int(sample["valid_mask"].sum())
@@ -426,56 +551,9 @@ class StreamRunner:
         dev["ready"].record(torch.cuda.current_stream(self.device))
         return dev
 
-    @torch.no_grad()
-    def _upload_raw(self, scan):
-        """Host scan -> device, once per scan object (a window re-uses the scans of the previous frames), through a small
-        ring of pinned staging buffers: a copy from pageable memory would hold the host until the stream has drained, and
-        pinning per call costs milliseconds."""
-        cache = self.__dict__.setdefault("_raw_cache", collections.OrderedDict())
-        cur = torch.cuda.current_stream(self.device)
-        hit = cache.get(id(scan))
-        if hit is not None and hit[0] is scan:
-            # the copy may still be in flight on ANOTHER stream (the window of frame t is uploaded on main, the look-ahead
-            # window of frame t+1 re-uses two of its scans on the side stream, and the other way round when the look-ahead
-            # misses): order this stream behind the copy and tell the allocator about the second user
-            _, dev, done, owner = hit
-            if owner != cur.cuda_stream:
-                cur.wait_event(done)
-                dev.record_stream(cur)
-            return dev
-        host = scan if torch.is_tensor(scan) else torch.from_numpy(np.ascontiguousarray(scan, dtype=np.float32))
-        if host.is_cuda:
-            return host
-        if not host.is_pinned():
-            ring = self.__dict__.setdefault("_raw_ring", {"slots": [], "next": 0})
-            if len(ring["slots"]) < 8:
-                ring["slots"].append([torch.empty(max(host.numel(), 4 * 160000), dtype=torch.float32).pin_memory(), None])
-                slot = ring["slots"][-1]
-            else:
-                slot = ring["slots"][ring["next"] % 8]
-                ring["next"] += 1
-            if slot[1] is not None:
-                slot[1].synchronize()                       # the copy that last used this buffer (8 uploads ago)
-            if slot[0].numel() < host.numel():
-                slot[0] = torch.empty(host.numel(), dtype=torch.float32).pin_memory()
-            staged = slot[0][:host.numel()].view(host.shape)
-            staged.copy_(host)
-            dev = staged.to(self.device, non_blocking=True)
-            slot[1] = torch.cuda.Event()
-            slot[1].record(cur)
-            done = slot[1]
-        else:
-            dev = host.to(self.device, non_blocking=True)
-            done = torch.cuda.Event()
-            done.record(cur)
-        cache[id(scan)] = (scan, dev, done, cur.cuda_stream)
-        while len(cache) > 16:
-            cache.popitem(last=False)
-        return dev
-
     def _build_raw(self, scans, poses):
         """H2D of the raw scans not yet on the device + device preprocessing, on the CURRENT stream."""
-        dev_scans = [self._upload_raw(s) for s in scans]
+        dev_scans = [self._uploads.upload(s) for s in scans]
         inv_cur = np.linalg.inv(np.asarray(poses[0], dtype=np.float64))
         # the current scan also goes through inv(P_cur) * P_cur, which is the identity only up to rounding
         # (the reference does exactly that, datasets/data_StreamMOS.py:424-467)
@@ -490,10 +568,10 @@ class StreamRunner:
         frame's window (pipeline mode): its upload, preprocessing and encoder run on the side stream beside this frame's
         decoder, and the next call (whose ``scans[0]`` must be the same object as this ``next_scans[0]``) picks them up."""
         from .device_preprocess import DevicePreprocessor
-        if getattr(self, "_pre", None) is None or self._pre.N != frame_point_num:
+        if self._pre is None or self._pre.N != frame_point_num:
             self._pre = DevicePreprocessor(self.device, frame_point_num=frame_point_num)
             self._raw_ahead = None
-        ahead, self._raw_ahead = getattr(self, "_raw_ahead", None), None
+        ahead, self._raw_ahead = self._raw_ahead, None
         built = ahead[1] if ahead is not None and ahead[0] is scans[0] else self._build_raw(scans, poses)
         nxt = None
         if next_scans is not None and self.pipeline and not self.use_graph:
@@ -514,50 +592,13 @@ class StreamRunner:
     def check_last_raw_sample(self):
         """The device preprocessing drops points beyond frame_point_num instead of raising (no sync on the hot path);
         call this where the labels are read back anyway to get the host path's error (preprocess.pad_scan)."""
-        built = getattr(self, "_last_built", None)
-        if built is not None and getattr(self, "_pre", None) is not None:
-            self._pre.check_capacity(built)
+        if self._last_built is not None:
+            self._pre.check_capacity(self._last_built)
 
     def last_in_range_counts(self):
         """Device int32 [T]: the in-range point count of every scan of the last step_raw window (no synchronisation; a
         count >= frame_point_num is the error check_last_raw_sample raises)."""
         return self._last_built["in_range_counts"]
-
-    def _pipelined(self, dev, next_dev):
-        """Two HIP streams: encode(t+1) on the side stream while frame t is decoded on the main one.  (Putting the serial
-        [third BEV stage -> temporal fusion] chain on a third stream of its own was measured too: 144 vs 146 scans/s, so
-        the simpler two-stream schedule stays.)"""
-        eng = self.model._engine_for(dev["pcds_xyzi"])
-        if eng is None:
-            raise RuntimeError("StreamRunner(pipeline=True) needs the fused GPU engine (eval mode, fast_inference)")
-        main = torch.cuda.current_stream(self.device)
-        if self._pre_enc is not None and self._pre_enc[0] is dev:
-            enc = self._pre_enc[1]
-            main.wait_stream(self._side)               # encoder of this frame, issued during the previous step
-        else:
-            enc = eng.encode(dev["pcds_xyzi"], dev["pcds_coord"], dev["pcds_sphere_coord"],
-                             n_live=dev.get("n_live") if self.skip_padding else None)
-        self._pre_enc = None
-        if next_dev is not None:                        # encoder of the NEXT frame, concurrent with this decode
-            # the side stream must start behind the producers of next_dev.  Inputs made by upload() carry the event
-            # recorded behind their H2D copies; anything else (e.g. device preprocessing on main) is ordered behind
-            # main's whole tail.  Two encodes of one engine may run concurrently (frame 0: encode(t) on main beside
-            # encode(t+1) here): every piece of engine scratch is keyed by stream (engine._block_ws, ops._stream_workspace).
-            ready = next_dev.get("ready")
-            if ready is not None:
-                self._side.wait_event(ready)
-            else:
-                self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):
-                nxt = eng.encode(next_dev["pcds_xyzi"], next_dev["pcds_coord"], next_dev["pcds_sphere_coord"],
-                                 n_live=next_dev.get("n_live") if self.skip_padding else None)
-            for t in list(nxt.values()) + [next_dev[k] for k in self._KEYS]:
-                if torch.is_tensor(t):
-                    t.record_stream(main)
-                    t.record_stream(self._side)
-            self._pre_enc = (next_dev, nxt)
-        return eng.decode(enc, self.memory if self.frame > 0 else None, want_aux=False,       # the runner uses pred_cls only
-                          n_live=dev.get("n_live") if self.skip_padding else None)
 
     @torch.no_grad()
     def step(self, dev, pose=None, next_dev=None):
@@ -571,40 +612,23 @@ class StreamRunner:
             labels = ops.tta_argmax(pred_cls)
             self.memory = [grp["mem"] for grp in self._groups]
         else:
-            if self.pipeline:
-                res = self._pipelined(dev, next_dev)
-            else:
-                eng = self.model._engine_for(dev["pcds_xyzi"])
-                if eng is not None:
-                    # the same kernels as the pipelined form, one stream: encode, then decode without the three aux heads the
-                    # runner never reads (model.infer computes them: 3 GEMMs + 2 resizes per frame that the two-stream step does
-                    # not run, so serial traces would not be traces of the timed step)
-                    enc = eng.encode(dev["pcds_xyzi"], dev["pcds_coord"], dev["pcds_sphere_coord"],
-                                     n_live=dev.get("n_live") if self.skip_padding else None)
-                    res = eng.decode(enc, self.memory if self.frame > 0 else None, want_aux=False,
-                                     n_live=dev.get("n_live") if self.skip_padding else None)
-                else:
-                    batch = {k: dev[k].unsqueeze(0) for k in ("pcds_xyzi", "pcds_coord", "pcds_sphere_coord")}
-                    res = self.model.infer(batch, self.frame, self.memory)
+            # pipeline=False runs the same kernels on one stream: encode, then decode without the three aux heads the runner
+            # never reads (model.infer computes them: 3 GEMMs + 2 resizes per frame that the two-stream step does not run,
+            # so serial traces would not be traces of the timed step)
+            res = self._encode_decode(dev, next_dev)
+            if res is None:
+                res = self.model.infer({k: dev[k].unsqueeze(0) for k in _KEYS}, self.frame, self.memory)
             pred_cls, self.memory = res[0], res[-1]          # 5-tuple (stage 1) or 6-tuple (StreamMOS_seg)
             labels = ops.tta_argmax(pred_cls)
             if len(res) == 6:
                 bf_labels = ops.tta_argmax(res[1])            # val_StreamMOS_seg.py:101-103
         out = {"pred_cls": pred_cls, "labels": labels, "voted": []}
+        raw = raw_labels(labels, dev, self._pre)
         if bf_labels is not None:
             out["bf_pred_cls"], out["bf_labels"] = res[1], bf_labels
-        raw = None
-        if "prefix" in dev:                                                       # device-preprocessed sample
-            raw = self._pre.unpad_labels(labels, dev)
-        elif "valid_index" in dev:
-            raw = torch.zeros(dev["n_raw"], dtype=torch.uint8, device=self.device)
-            raw.index_copy_(0, dev["valid_index"], labels[:dev["n_valid"]])      # val_StreamMOS.py:112-118
-        if bf_labels is not None and "prefix" in dev:
-            out["bf_raw_labels"] = self._pre.unpad_labels(bf_labels, dev)
-        elif bf_labels is not None and "valid_index" in dev:     # the `_bf` prediction file of val_StreamMOS_seg.py:128-131,141
-            bf_raw = torch.zeros(dev["n_raw"], dtype=torch.uint8, device=self.device)
-            bf_raw.index_copy_(0, dev["valid_index"], bf_labels[:dev["n_valid"]])
-            out["bf_raw_labels"] = bf_raw
+            bf_raw = raw_labels(bf_labels, dev, self._pre)    # the `_bf` prediction file of val_StreamMOS_seg.py:128-131,141
+            if bf_raw is not None:
+                out["bf_raw_labels"] = bf_raw
         if raw is not None:
             out["raw_labels"] = raw
             if self.voter is not None and "raw_scan" in dev:
@@ -619,7 +643,7 @@ class StreamRunner:
         return out
 
 
-class MultiStreamRunner:
+class MultiStreamRunner(_TwoStreamRunner):
     """S independent sequences advanced in lock step as ONE batch of S x V samples (BASELINE.json configs[2]:
     concurrent sequences on one GPU, every stream's recurrent memory and voting window resident in HBM).
     Streams never interact: the network is batch-independent, the TTA reduce and the voting run per stream."""
@@ -628,62 +652,37 @@ class MultiStreamRunner:
         """pipeline=True: as StreamRunner(pipeline=True) -- step(batched, poses, next_batched=...) runs the encoder of the NEXT batch
         on a second HIP stream beside the decoder of the current one, and the three aux heads nobody reads are not computed.
         Same kernels, same results as pipeline=False.  conv_precision: as StreamRunner."""
-        self.device = torch.device(device)
-        self.model = model.to(self.device).eval()
-        set_conv_precision(self.model, conv_precision)
+        # skip_padding=False: the batch computes every logit (the streams' padding tails differ)
+        super().__init__(model, device, conv_precision, pipeline, skip_padding=False)
         self.n = n_streams
         self.voters = [VoxelVoter(self.device) for _ in range(n_streams)] if vote else None
-        self.memory = None
-        self.frame = 0
-        self.pipeline = pipeline
-        self._side = concurrent_stream(self.device) if pipeline else None
-        self._pre_enc = None
+        self.reset()
+
+    def reset(self):
+        """A new set of sequences: additionally every voting window starts over."""
+        super().reset()
+        for voter in self.voters or ():
+            voter.reset()
 
     @staticmethod
     def batch_inputs(devs):
         """list of per-stream uploads (StreamRunner.upload) -> one batched dict (concatenated along the TTA dim)."""
-        out = {k: torch.cat([d[k] for d in devs], 0) for k in ("pcds_xyzi", "pcds_coord", "pcds_sphere_coord")}
+        out = {k: torch.cat([d[k] for d in devs], 0) for k in _KEYS}
         out["streams"] = [{k: d[k] for k in d if k not in out} for d in devs]
         return out
-
-    _KEYS = ("pcds_xyzi", "pcds_coord", "pcds_sphere_coord")
-
-    def _pipelined(self, batched, next_batched):
-        eng = self.model._engine_for(batched["pcds_xyzi"])
-        if eng is None:
-            raise RuntimeError("MultiStreamRunner(pipeline=True) needs the fused GPU engine (eval mode, fast_inference)")
-        main = torch.cuda.current_stream(self.device)
-        if self._pre_enc is not None and self._pre_enc[0] is batched:
-            enc = self._pre_enc[1]
-            main.wait_stream(self._side)
-        else:
-            enc = eng.encode(*(batched[k] for k in self._KEYS))
-        self._pre_enc = None
-        if next_batched is not None:
-            self._side.wait_stream(main)          # behind whatever produced next_batched (batch_inputs runs on the main stream)
-            with torch.cuda.stream(self._side):
-                nxt = eng.encode(*(next_batched[k] for k in self._KEYS))
-            for t in list(nxt.values()) + [next_batched[k] for k in self._KEYS]:
-                if torch.is_tensor(t):
-                    t.record_stream(main)
-                    t.record_stream(self._side)
-            self._pre_enc = (next_batched, nxt)
-        return eng.decode(enc, self.memory if self.frame > 0 else None, want_aux=False)
 
     @torch.no_grad()
     def step(self, batched, poses, next_batched=None):
         if self.pipeline:
-            res = self._pipelined(batched, next_batched)
-        else:
-            batch = {k: batched[k].unsqueeze(0) for k in self._KEYS}
-            res = self.model.infer(batch, self.frame, self.memory)
+            res = self._encode_decode(batched, next_batched)
+        else:                                           # the module graph's forward, aux heads included
+            res = self.model.infer({k: batched[k].unsqueeze(0) for k in _KEYS}, self.frame, self.memory)
         pred_cls, self.memory = res[0], res[-1]
         v = pred_cls.shape[0] // self.n
         outs = []
         for s, meta in enumerate(batched["streams"]):
             labels = ops.tta_argmax(pred_cls[s * v:(s + 1) * v])
-            raw = torch.zeros(meta["n_raw"], dtype=torch.uint8, device=self.device)
-            raw.index_copy_(0, meta["valid_index"], labels[:meta["n_valid"]])
+            raw = raw_labels(labels, meta)
             voted = []
             if self.voters is not None and "raw_scan" in meta:
                 voted = self.voters[s].push(meta["raw_scan"], raw, poses[s])

@@ -457,53 +457,126 @@ def test_concurrent_streams_equal_separate_streams(model):
         solo.append(outs)
     ms = streaming.MultiStreamRunner(model, DEV, n_streams=2, vote=False)
     msp = streaming.MultiStreamRunner(model, DEV, n_streams=2, vote=False, pipeline=True)      # two HIP streams, one batch of look-ahead
+    declared = set(vars(msp))
     up = streaming.StreamRunner(model, DEV, vote=False)
-    batches = []
+    uploads, batches, kept = [], [], []
     for i in range(3):
         devs = []
         for scans, poses in seqs:
             idx = preprocess.window_indices(i, 6, 3)
             sample = preprocess.build_sample([scans[j] for j in idx], [poses[j] for j in idx], 2048, spec, tta=True)
             devs.append(up.upload(sample, scans[i]))
+        uploads.append(devs)
         batches.append(ms.batch_inputs(devs))
     for i in range(3):
         pred, outs = ms.step(batches[i], [seqs[q][1][i] for q in range(2)])
         pred_p, outs_p = msp.step(batches[i], [seqs[q][1][i] for q in range(2)], next_batched=batches[i + 1] if i + 1 < 3 else None)
         assert torch.equal(pred_p, pred) and all(torch.equal(a["raw_labels"], b["raw_labels"]) for a, b in zip(outs_p, outs))
+        kept.append((pred.clone(), [o["raw_labels"].clone() for o in outs]))
         for q in range(2):
             want_pred, want_raw = solo[q][i]
             err = (pred[4 * q:4 * q + 4] - want_pred).abs().max().item() / want_pred.abs().max().item()
             flips = int((outs[q]["raw_labels"] != want_raw).sum().item())
             print("2 streams, frame %d, stream %d: batched vs solo %.2e of range, %d labels differ" % (i, q, err, flips))
             assert err <= 1e-5 and flips == 0, (i, q, err, flips)
+    # the same sequences once more after reset(); batch 1 arrives re-made (another object than the one announced), so its
+    # encoder issued ahead is dropped and it is encoded again on the main stream
+    assert msp.frame == 3 and set(vars(msp)) == declared
+    msp.reset()
+    assert msp.frame == 0 and msp.memory is None and set(vars(msp)) == declared
+    for i in range(3):
+        cur = ms.batch_inputs(uploads[i]) if i == 1 else batches[i]
+        pred_p, outs_p = msp.step(cur, [seqs[q][1][i] for q in range(2)], next_batched=batches[i + 1] if i + 1 < 3 else None)
+        pred, raws = kept[i]
+        assert torch.equal(pred_p, pred) and all(torch.equal(a["raw_labels"], b) for a, b in zip(outs_p, raws))
 
 
 def test_pipelined_runner_equals_plain_runner(model):
     """pipeline=True overlaps the encoder of frame t+1 with the decoder of frame t on a second HIP stream; results
-    must equal the serial runner's (same kernels, same inputs), frame after frame, including the voting output."""
+    must equal the serial runner's (same kernels, same inputs), frame after frame, including the voting output.
+    Second pass ("miss"): frame 2 arrives as a fresh upload of the sample that was announced, another dict object -- the
+    encoder issued ahead is dropped and the frame is encoded again on the main stream; same results.  Every pass is given
+    the next frame's inputs: the serial runner must not look ahead."""
     spec = preprocess.VoxelSpec()
     n_frames = 6
     scans = [synth.synthetic_scan(k, 16, 120) for k in range(n_frames + 2)]
     poses = [synth.synthetic_pose(k) for k in range(n_frames + 2)]
+    samples = []
+    for i in range(n_frames):
+        idx = preprocess.window_indices(i, n_frames + 2, 3)
+        samples.append(preprocess.build_sample([scans[j] for j in idx], [poses[j] for j in idx], 2048, spec, tta=True))
     res = {}
-    for pipe in (False, True):
-        runner = streaming.StreamRunner(model, DEV, vote=True, pipeline=pipe)
+    # which encodes run on the main stream: all of the serial runner's; frame 0 of the pipelined one; frame 2 again on a miss
+    on_main = {"plain": [True] * 6, "ahead": [True] + [False] * 5, "miss": [True, False, False, True, False, False, False]}
+    for mode in ("plain", "ahead", "miss"):
+        runner = streaming.StreamRunner(model, DEV, vote=True, pipeline=mode != "plain")
         runner.voter.window = 3
-        devs = []
-        for i in range(n_frames):
-            idx = preprocess.window_indices(i, n_frames + 2, 3)
-            sample = preprocess.build_sample([scans[j] for j in idx], [poses[j] for j in idx], 2048, spec, tta=True)
-            devs.append(runner.upload(sample, scans[i]))
+        devs = [runner.upload(samples[i], scans[i]) for i in range(n_frames)]
+        with torch.no_grad():
+            eng = model._engine_for(devs[0]["pcds_xyzi"])
+        encode, streams = eng.encode, []
+
+        def spy(*args, **kwargs):
+            streams.append(torch.cuda.current_stream().cuda_stream)
+            return encode(*args, **kwargs)
+        main = torch.cuda.current_stream().cuda_stream
         outs = []
-        for i in range(n_frames):
-            o = runner.step(devs[i], poses[i], next_dev=devs[i + 1] if i + 1 < n_frames else None)
-            outs.append((o["pred_cls"].clone(), o["raw_labels"].clone(), [(f, l.clone()) for f, l in o["voted"]]))
+        with mock.patch.object(eng, "encode", spy):
+            for i in range(n_frames):
+                cur = runner.upload(samples[i], scans[i]) if (mode, i) == ("miss", 2) else devs[i]
+                o = runner.step(cur, poses[i], next_dev=devs[i + 1] if i + 1 < n_frames else None)
+                outs.append((o["pred_cls"].clone(), o["raw_labels"].clone(), [(f, l.clone()) for f, l in o["voted"]]))
         torch.cuda.synchronize()
-        res[pipe] = outs
-    for (p0, r0, v0), (p1, r1, v1) in zip(res[False], res[True]):
-        assert torch.equal(p0, p1) or (p0 - p1).abs().max().item() <= 1e-6 * p0.abs().max().item()
-        assert torch.equal(r0, r1)
+        assert [s == main for s in streams] == on_main[mode], (mode, streams, main)
+        res[mode] = outs
+    for mode in ("ahead", "miss"):
+        for (p0, r0, v0), (p1, r1, v1) in zip(res["plain"], res[mode]):
+            assert torch.equal(p0, p1) or (p0 - p1).abs().max().item() <= 1e-6 * p0.abs().max().item()
+            assert torch.equal(r0, r1)
+            assert [f for f, _ in v0] == [f for f, _ in v1] and all(torch.equal(a[1], b[1]) for a, b in zip(v0, v1))
+
+
+def test_reset_with_a_look_ahead_pending_starts_a_clean_sequence(model):
+    """Three frames of sequence A through a pipelined runner, the last of which wrongly announces a successor, so an
+    encoder is pending on the side stream; reset(); three frames of sequence B.  B's logits, raw labels and votes equal a
+    fresh pipelined runner's bit for bit, the runner restarts at frame 0 without memory, and it holds the same attributes
+    after construction, after the steps and after reset()."""
+    spec = preprocess.VoxelSpec()
+    seqs = []
+    for q in range(2):
+        scans = [synth.synthetic_scan(70 * q + k, 16, 120) for k in range(4)]
+        poses = [synth.synthetic_pose(k) for k in range(4)]
+        samples = []
+        for i in range(4):
+            idx = preprocess.window_indices(i, 4, 3)
+            samples.append(preprocess.build_sample([scans[j] for j in idx], [poses[j] for j in idx], 2048, spec, tta=True))
+        seqs.append((scans, poses, samples))
+
+    def run(runner, seq, announce_past_the_end):
+        scans, poses, samples = seq
+        devs = [runner.upload(samples[i], scans[i]) for i in range(4)]
+        outs = []
+        for i in range(3):
+            o = runner.step(devs[i], poses[i], next_dev=devs[i + 1] if i < 2 or announce_past_the_end else None)
+            outs.append((o["pred_cls"].clone(), o["raw_labels"].clone(), [(f, l.clone()) for f, l in o["voted"]]))
+        return outs
+
+    runner = streaming.StreamRunner(model, DEV, vote=True, pipeline=True)
+    runner.voter.window = 3
+    declared = set(vars(runner))
+    run(runner, seqs[0], True)
+    assert runner.frame == 3 and runner.memory is not None and set(vars(runner)) == declared
+    runner.reset()
+    assert runner.frame == 0 and runner.memory is None and set(vars(runner)) == declared
+    got = run(runner, seqs[1], False)
+    fresh = streaming.StreamRunner(model, DEV, vote=True, pipeline=True)
+    fresh.voter.window = 3
+    want = run(fresh, seqs[1], False)
+    torch.cuda.synchronize()
+    for (p0, r0, v0), (p1, r1, v1) in zip(want, got):
+        assert torch.equal(p0, p1) and torch.equal(r0, r1)
         assert [f for f, _ in v0] == [f for f, _ in v1] and all(torch.equal(a[1], b[1]) for a, b in zip(v0, v1))
+    assert len(got[2][2]) == 3                # the window of 3 voted: B's votes saw none of A's frames
 
 
 def test_seg_variant_engine_matches_reference_golden(golden):

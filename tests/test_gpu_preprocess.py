@@ -78,7 +78,9 @@ def test_step_raw_equals_host_preprocessed_step():
 def test_step_raw_with_look_ahead_equals_plain_step_raw():
     """step_raw(next_scans=...) uploads, preprocesses and encodes the following frame on the side stream beside the current
     frame's decoder; labels, logits and voted frames must be those of the serial raw path, bit for bit (host arrays and
-    device-resident scans; the last frame has no successor)."""
+    device-resident scans; the last frame has no successor).  Frame 3 arrives as a copy of the scan that was announced: the
+    window prepared ahead and its encoder are dropped and the frame is built again on the main stream, same results.  The
+    runner holds the same attributes after the steps as after construction."""
     from streammos_amd import streaming
     from streammos_amd.refapi.config import StreamMOS as cfg
     from streammos_amd.refapi.models import StreamMOS
@@ -91,13 +93,18 @@ def test_step_raw_with_look_ahead_equals_plain_step_raw():
         plain = streaming.StreamRunner(model, DEV, vote=True)
         ahead = streaming.StreamRunner(model, DEV, vote=True, pipeline=True)
         plain.voter.window = ahead.voter.window = 3
+        declared = set(vars(ahead))
         for i in range(6):
             idx = preprocess.window_indices(i, 7, 3)
             nxt = preprocess.window_indices(i + 1, 7, 3) if i < 5 else None
             oa = plain.step_raw([src[j] for j in idx], [poses[j] for j in idx], frame_point_num=2048)
-            ob = ahead.step_raw([src[j] for j in idx], [poses[j] for j in idx], frame_point_num=2048,
+            window = [src[j] for j in idx]
+            if i == 3:
+                window[0] = window[0].clone() if on_device else window[0].copy()
+            ob = ahead.step_raw(window, [poses[j] for j in idx], frame_point_num=2048,
                                 next_scans=[src[j] for j in nxt] if nxt else None,
                                 next_poses=[poses[j] for j in nxt] if nxt else None)
+            assert set(vars(ahead)) == declared
             assert torch.equal(oa["pred_cls"], ob["pred_cls"]) and torch.equal(oa["raw_labels"], ob["raw_labels"])
             assert [f for f, _ in oa["voted"]] == [f for f, _ in ob["voted"]]
             for (_, la), (_, lb) in zip(oa["voted"], ob["voted"]):

@@ -175,6 +175,24 @@ def test_vote_history_window_follows_the_reference():
     assert streaming.vote_history_ids(5) == [0, 1, 2, 3, 4, 6, 7]
 
 
+def test_streaming_state_is_declared_up_front():
+    """reset() empties what the constructor declared; it neither adds nor removes an attribute."""
+    uploads = streaming.ScanUploads(torch.device("cpu"))
+    declared = set(vars(uploads))
+    scan = np.zeros((5, 4), dtype=np.float32)
+    uploads.cache[id(scan)] = (scan, None, None, 0)
+    uploads.slots.append([torch.empty(4), None])
+    uploads.next = 3
+    uploads.reset()
+    assert set(vars(uploads)) == declared and not uploads.cache and len(uploads.slots) == 1 and uploads.next == 3
+    voter = streaming.VoxelVoter("cpu")
+    declared = set(vars(voter))
+    voter.frames[0] = (None, None, np.eye(4))
+    voter.next_id = 1
+    voter.reset()
+    assert set(vars(voter)) == declared and not voter.frames and voter.next_id == 0
+
+
 def test_window_indices_follow_dataloadval():
     assert preprocess.window_indices(0, 100, 3) == [0, 1, 2]
     assert preprocess.window_indices(1, 100, 3) == [1, 2, 3]
