@@ -673,6 +673,9 @@ int smos_unbalance_block_cl(const float* x, int64_t x_pitch, const float* ua, co
  * theirs with torch.zeros inside VoxelMaxPool, deep_point/point_deep.py:27). */
 int smos_zero_views_cl(int32_t n, float* const* ptrs, const int64_t* rows, const int64_t* row_floats, const int64_t* pitches,
                        smos_stream_t stream);
+/* Bilinear (align_corners=True) resize of n_src <= 3 channels-last sources to Ho x Wo, concatenated along C into the dense
+ * out [B, Ho, Wo, sum src_c].  Every source: 16-byte aligned, src_c % 4 == 0, src_h, src_w > 0, src_pitch % 4 == 0 and
+ * src_pitch >= src_c; out 16-byte aligned. */
 int smos_upsample_concat_cl(const float* const* src, const int64_t* src_c, const int64_t* src_h, const int64_t* src_w,
                             const int64_t* src_pitch, int32_t n_src, float* out, int64_t B, int64_t Ho, int64_t Wo,
                             smos_stream_t stream);

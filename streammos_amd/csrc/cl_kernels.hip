@@ -617,11 +617,14 @@ extern "C" int smos_upsample_concat_cl(const float* const* src, const int64_t* s
                                        smos_stream_t stream) {
   SMOS_REQUIRE(n_src >= 1 && n_src <= 3 && B > 0 && Ho > 0 && Wo > 0 && src && src_c && src_h && src_w && src_pitch && out,
                "upsample_concat_cl: bad arguments");
+  SMOS_REQUIRE(al16(out), "upsample_concat_cl: the output must be 16-byte aligned");
   UpSrcCl s[3];
   int ctot = 0;
   for (int i = 0; i < 3; ++i) {
     if (i < n_src) {
       SMOS_REQUIRE(src[i] && al16(src[i]) && src_c[i] > 0 && src_c[i] % 4 == 0 && src_pitch[i] % 4 == 0, "upsample_concat_cl: bad source %d", i);
+      SMOS_REQUIRE(src_h[i] > 0 && src_w[i] > 0 && src_pitch[i] >= src_c[i],
+                   "upsample_concat_cl: source %d needs a positive size and a row pitch of at least its channels", i);
       s[i] = UpSrcCl{src[i], (int)src_c[i], (int)src_h[i], (int)src_w[i], src_pitch[i]};
       ctot += (int)src_c[i];
     } else {
