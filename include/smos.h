@@ -720,6 +720,31 @@ int smos_label_words(const uint8_t* labels, int64_t n, int32_t lut, int32_t* wor
 int smos_label_count_voted(const int32_t* voted, int64_t n, int32_t* words, const uint32_t* gt, const int32_t* gt_map,
                            int32_t map_n, uint64_t* counts, smos_stream_t stream);
 
+/* Training point MLP (csrc/point_mlp_train.hip): BN0 -> conv1x1 7->64 -> BN1 -> ReLU -> conv1x1 64->64 -> BN2 ->
+ * ReLU of PointNetStacker(7, 64, pre_bn=True, stack_num=2) on x [S,7,N] -> y [S,64,N], both channel-major float32.
+ *   params     HOST array of 14 DEVICE float pointers: gamma0, beta0, running_mean0, running_var0, W1 [64,7], gamma1, beta1,
+ *              running_mean1, running_var1, W2 [64,64], gamma2, beta2, running_mean2, running_var2
+ *   eps_mom    HOST array of 6 doubles: eps of BN0..2, then momentum of BN0..2
+ *   training   != 0: batch statistics over the S*N points (biased variance), the six running buffers updated in place
+ *              (running_var with the unbiased variance); S*N must exceed 1.  0: the running buffers are the statistics.
+ *   fold       smos_point_mlp_fold_floats() floats, dstat smos_point_mlp_stat_doubles() doubles: written by the forward, read
+ *              by the backward; together with x they are all the backward needs from the forward.
+ *   grads      HOST array of 8 DEVICE float pointers, NULL where no gradient is wanted: gamma0, beta0, W1, gamma1, beta1, W2,
+ *              gamma2, beta2.  Work that only a NULL entry needs is not done.  There is no gradient for x.
+ *   work       smos_point_mlp_work_bytes(S*N) bytes of device scratch (-1 from the query: too many points).
+ * Every sum over points is formed per chunk of smos_point_mlp_chunk() points and added in chunk order in float64: the bits of
+ * y, of the buffers and of every gradient depend on the data alone, not on the grid (smos_debug_set_conv_grid_cap bounds the
+ * grids of the chunk walks) or the run.  Nothing is read back to the host. */
+int32_t smos_point_mlp_chunk(void);
+int32_t smos_point_mlp_fold_floats(void);
+int32_t smos_point_mlp_stat_doubles(void);
+int64_t smos_point_mlp_work_bytes(int64_t P);
+int smos_point_mlp_fwd(const float* x, int64_t S, int64_t N, int32_t training, const void* const* params, const double* eps_mom,
+                       float* y, float* fold, double* dstat, void* work, int64_t work_bytes, smos_stream_t stream);
+int smos_point_mlp_bwd(const float* x, const float* grad_y, int64_t S, int64_t N, int32_t training, const void* const* params,
+                       const double* eps_mom, const float* fold, const double* dstat, void* const* grads, void* work,
+                       int64_t work_bytes, smos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

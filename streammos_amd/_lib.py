@@ -109,6 +109,12 @@ SIGNATURES = {
     "smos_gather_scatter_cl_live": [vp, i64, vp, i32, c_f32p, vp, i32, c_f32p, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp],
     "smos_label_words": [vp, i64, i32, vp, vp, vp, i32, vp, vp],
     "smos_label_count_voted": [vp, i64, vp, vp, vp, i32, vp, vp],
+    "smos_point_mlp_chunk": [],
+    "smos_point_mlp_fold_floats": [],
+    "smos_point_mlp_stat_doubles": [],
+    "smos_point_mlp_work_bytes": [i64],
+    "smos_point_mlp_fwd": [vp, i64, i64, i32, ctypes.POINTER(vp), c_f64p, vp, vp, vp, vp, i64, vp],
+    "smos_point_mlp_bwd": [vp, vp, i64, i64, i32, ctypes.POINTER(vp), c_f64p, vp, vp, ctypes.POINTER(vp), vp, i64, vp],
 }
 
 ABI_VERSION = 1      # SMOS_ABI_VERSION of the include/smos.h these signatures were written against
@@ -141,7 +147,10 @@ def load():
         raise RuntimeError("streammos_amd: %s has ABI version %d, this package binds version %d -- rebuild it "
                            "(`python -m streammos_amd.build -f`)" % (LIB_PATH, have, ABI_VERSION))
     for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)
+        fn = getattr(lib, name, None)
+        if fn is None:          # additions keep the ABI version: an older build of the same version lacks the newer entries
+            raise RuntimeError("streammos_amd: %s has no %s -- it was built from an older tree; rebuild it "
+                               "(`python -m streammos_amd.build -f`)" % (LIB_PATH, name))
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int
     lib.smos_dbscan_work_bytes.restype = ctypes.c_int64
@@ -152,6 +161,7 @@ def load():
     lib.smos_msda_bwd_det_work_bytes.restype = ctypes.c_int64
     lib.smos_train_prep_work_bytes.restype = ctypes.c_int64
     lib.smos_copy_paste_work_bytes.restype = ctypes.c_int64
+    lib.smos_point_mlp_work_bytes.restype = ctypes.c_int64
     lib.smos_conv_cl_sum_chunks.restype = ctypes.c_int64
     lib.smos_conv_wino_sum_chunks.restype = ctypes.c_int64
     lib.smos_basic_block_ws_floats.restype = ctypes.c_int64

@@ -362,6 +362,134 @@ def seg_loss(pred, target, top_ratio=0.2, top_weight=4.0, ignore_index=0, lovasz
         return _SegLoss.apply(pred3, tgt, k, float(top_weight), int(ignore_index), float(lovasz_weight))
 
 
+_point_mlp_fused = None
+
+
+def set_point_mlp_fused(flag):
+    """Explicit setting of ``point_mlp_fused`` (True / False), or None to hand the decision back to the environment.
+    Returns the previous explicit setting."""
+    global _point_mlp_fused
+    prev, _point_mlp_fused = _point_mlp_fused, (None if flag is None else bool(flag))
+    return prev
+
+
+def point_mlp_fused():
+    """Whether PointNetStacker.forward (refapi/networks/backbone.py) may route a supported configuration to
+    ``point_mlp_train``: the ``set_point_mlp_fused`` setting if there is one, else ``SMOS_POINT_MLP`` in the environment
+    (default 0), read per call."""
+    if _point_mlp_fused is not None:
+        return _point_mlp_fused
+    return os.environ.get("SMOS_POINT_MLP", "0").strip().lower() not in ("", "0", "false", "off", "no")
+
+
+def point_mlp_chunk():
+    """Points per chunk of partial sums of ``point_mlp_train`` (tests place their shapes around it)."""
+    return int(_lib.load().smos_point_mlp_chunk())
+
+
+def _point_mlp_ptrs(tensors):
+    return (_lib.vp * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+class _PointMlpTrain(torch.autograd.Function):
+    """ops.point_mlp_train: one foreign call per direction.  Kept for the backward: x, the parameters, and the folded
+    statistics the forward leaves on the device (a few thousand floats) -- no activation."""
+
+    @staticmethod
+    def forward(ctx, x, g0, b0, w1, g1, b1, w2, g2, b2, buffers, eps_mom, training):
+        lib = _lib.load()
+        s, _, n = x.shape[:3]
+        dev = x.device
+        need = int(lib.smos_point_mlp_work_bytes(s * n))
+        if need <= 0:
+            raise RuntimeError("point_mlp_train: %d x %d points is more than the kernels are set up for" % (s, n))
+        work = _stream_workspace("point_mlp", (need,), torch.uint8, dev)
+        y = torch.empty((s, 64, n, 1), dtype=torch.float32, device=dev)
+        fold = torch.empty(int(lib.smos_point_mlp_fold_floats()), dtype=torch.float32, device=dev)
+        dstat = torch.empty(int(lib.smos_point_mlp_stat_doubles()), dtype=torch.float64, device=dev)
+        rm0, rv0, rm1, rv1, rm2, rv2 = buffers
+        params = (g0, b0, rm0, rv0, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2)
+        with _on(dev), profiling.span_f("point_mlp_%s[%dx%d]", ("train" if training else "eval", s, n)):
+            rc = lib.smos_point_mlp_fwd(x.data_ptr(), s, n, int(training), _point_mlp_ptrs(params), _lib.f64_array(eps_mom),
+                                        y.data_ptr(), fold.data_ptr(), dstat.data_ptr(), work.data_ptr(), need, _stream(x))
+        _lib.check(rc, "smos_point_mlp_fwd")
+        ctx.save_for_backward(x, g0, b0, w1, g1, b1, w2, g2, b2, fold, dstat)
+        ctx.buffers, ctx.eps_mom, ctx.training = buffers, eps_mom, bool(training)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, g0, b0, w1, g1, b1, w2, g2, b2, fold, dstat = ctx.saved_tensors
+        lib = _lib.load()
+        s, _, n = x.shape[:3]
+        dev = x.device
+        gy = grad_y.to(torch.float32).contiguous()
+        rm0, rv0, rm1, rv1, rm2, rv2 = ctx.buffers
+        params = (g0, b0, rm0, rv0, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2)
+        grads = [torch.empty_like(p) if ctx.needs_input_grad[1 + i] else None for i, p in enumerate((g0, b0, w1, g1, b1, w2, g2, b2))]
+        if any(g is not None for g in grads):
+            need = int(lib.smos_point_mlp_work_bytes(s * n))
+            work = _stream_workspace("point_mlp", (need,), torch.uint8, dev)
+            with _on(dev), profiling.span_f("point_mlp_bwd[%dx%d]", (s, n)):
+                rc = lib.smos_point_mlp_bwd(x.data_ptr(), gy.data_ptr(), s, n, int(ctx.training), _point_mlp_ptrs(params),
+                                            _lib.f64_array(ctx.eps_mom), fold.data_ptr(), dstat.data_ptr(), _point_mlp_ptrs(grads),
+                                            work.data_ptr(), need, _stream(x))
+            _lib.check(rc, "smos_point_mlp_bwd")
+        return (None, *grads, None, None, None)
+
+
+def _point_mlp_weight(name, m, shape):
+    w = m.weight if isinstance(m, torch.nn.Module) else m
+    if isinstance(m, torch.nn.Module) and getattr(m, "bias", None) is not None:
+        raise RuntimeError("point_mlp_train: %s has a bias; the point MLP's convolutions have none" % name)
+    if tuple(w.shape[:2]) != shape or w.numel() != shape[0] * shape[1]:
+        raise RuntimeError("point_mlp_train: %s is %s, want a 1x1 convolution %d -> %d" % (name, tuple(w.shape), shape[1], shape[0]))
+    return w
+
+
+def point_mlp_train(x, bn0, conv1, bn1, conv2, bn2, training=None):
+    """BN0 -> 1x1 conv 7->64 -> BN1 -> ReLU -> 1x1 conv 64->64 -> BN2 -> ReLU of ``PointNetStacker(7, 64, pre_bn=True,
+    stack_num=2)`` as one autograd op on the HIP kernels of csrc/point_mlp_train.hip.
+
+    x [S,7,N(,1)] float32 on the GPU (no gradient flows to it); bn0/bn1/bn2 the BatchNorm modules (affine, with running
+    statistics and a momentum); conv1/conv2 the bias-free 1x1 convolutions or their weights.  ``training`` (None:
+    ``bn0.training``): batch statistics over all S*N points, the six running buffers and ``num_batches_tracked`` updated in
+    place as the modules would; otherwise the running statistics.  Returns [S,64,N,1] float32; differentiable in the eight
+    parameters.  Every sum runs in a fixed order (the bits do not depend on the grid or the run) and nothing is read back
+    to the host."""
+    _require_cuda("point_mlp_train", x)
+    if x.dtype != torch.float32:
+        raise RuntimeError("point_mlp_train: float32 only (got %s)" % x.dtype)
+    if x.dim() == 3:
+        x = x[..., None]
+    if x.dim() != 4 or x.shape[1] != 7 or x.shape[3] != 1 or x.shape[0] * x.shape[2] == 0:
+        raise RuntimeError("point_mlp_train: x is %s, want [S,7,N(,1)] with S*N > 0" % (tuple(x.shape),))
+    training = bool(bn0.training if training is None else training)
+    bns = (bn0, bn1, bn2)
+    for i, (bn, c) in enumerate(zip(bns, (7, 64, 64))):
+        if bn.weight is None or bn.bias is None or bn.running_mean is None or bn.running_var is None or bn.momentum is None:
+            raise RuntimeError("point_mlp_train: bn%d must be affine, track running statistics and have a momentum" % i)
+        if bn.weight.numel() != c:
+            raise RuntimeError("point_mlp_train: bn%d has %d channels, want %d" % (i, bn.weight.numel(), c))
+    w1 = _point_mlp_weight("conv1", conv1, (64, 7))
+    w2 = _point_mlp_weight("conv2", conv2, (64, 64))
+    tensors = [bn0.weight, bn0.bias, w1, bn1.weight, bn1.bias, w2, bn2.weight, bn2.bias]
+    buffers = tuple(b for bn in bns for b in (bn.running_mean, bn.running_var))
+    for t in tensors + list(buffers):
+        if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("point_mlp_train: parameters and buffers must be contiguous float32 tensors on %s" % x.device)
+    if training and x.shape[0] * x.shape[2] < 2:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (x.shape,))
+    eps_mom = tuple(float(bn.eps) for bn in bns) + tuple(float(bn.momentum) for bn in bns)
+    y = _PointMlpTrain.apply(x.detach().contiguous(), *tensors, buffers, eps_mom, training)
+    if training:
+        for bn in bns:
+            if bn.num_batches_tracked is not None:
+                bn.num_batches_tracked.add_(1)
+    return y
+
+
 def msda_fwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight):
     """value [N,S,M,D], shapes [L,2] int64 (device), level_start [L] int64 (device), loc [N,Lq,M,L,P,2],
     attn [N,Lq,M,L,P] -> [N,Lq,M*D]."""

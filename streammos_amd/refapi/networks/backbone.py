@@ -108,7 +108,48 @@ class PointNetStacker(nn.Module):
             mods.append(PointNet(cout, cout, False, post_act))
         self.layer = nn.Sequential(*mods)
 
+    def _fused_modules(self, x):
+        """(bn0, conv1, bn1, conv2, bn2) where ops.point_mlp_train computes this forward, else None: the switch is on
+        (ops.point_mlp_fused, SMOS_POINT_MLP, default 0), x is a CUDA float32 [S,7,N,1] that needs no gradient, the stack is
+        exactly pre_bn 7 -> 64 -> 64 with ReLU, no autocast, the module is training or gradients are enabled, and the batch
+        norms are single-process.  Everything else stays on the module path."""
+        if not ops.point_mlp_fused():
+            return None
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and not x.requires_grad and x.dim() == 4
+                and x.shape[1] == 7 and x.shape[3] == 1 and x.shape[0] * x.shape[2] > 0):
+            return None
+        if torch.is_autocast_enabled() or not (self.training or torch.is_grad_enabled()):
+            return None
+        if len(self.layer) != 2:
+            return None
+        a, b = list(self.layer[0].layer), list(self.layer[1].layer)
+        if len(a) != 4 or len(b) != 3:
+            return None
+        bn0, conv1, bn1, conv2, bn2 = a[0], a[1], a[2], b[0], b[1]
+        if not all(type(m) is nn.ReLU for m in (a[3], b[2])):
+            return None
+        for conv, cin in ((conv1, 7), (conv2, 64)):
+            if not (type(conv) is nn.Conv2d and conv.in_channels == cin and conv.out_channels == 64 and conv.bias is None
+                    and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
+                    and conv.weight.dtype == torch.float32 and conv.weight.device == x.device):
+                return None
+        for bn, c in ((bn0, 7), (bn1, 64), (bn2, 64)):
+            if type(bn) is nn.SyncBatchNorm:
+                dist = torch.distributed
+                if dist.is_available() and dist.is_initialized() and dist.get_world_size(bn.process_group) > 1:
+                    return None
+            elif type(bn) is not nn.BatchNorm2d:
+                return None
+            if not (bn.num_features == c and bn.affine and bn.track_running_stats and bn.momentum is not None
+                    and bn.running_mean is not None and bn.training == self.training
+                    and bn.weight.dtype == torch.float32 and bn.weight.device == x.device):
+                return None
+        return bn0, conv1, bn1, conv2, bn2
+
     def forward(self, x):
+        fused = self._fused_modules(x)
+        if fused is not None:
+            return ops.point_mlp_train(x, *fused, training=self.training)
         return self.layer(x)
 
 
