@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMOS_ABI_VERSION 1
+#define SMOS_ABI_VERSION 2
 
 enum smos_status {
   SMOS_OK = 0,
@@ -41,7 +41,7 @@ int smos_abi_version(void);
 const char* smos_last_error(void);
 /* Test hook (process-wide, not part of the data path; the one piece of state the library keeps): caps the grid of the
  * persistent convolution kernels (smos_conv_cl / _rows_cl / _wino_cl / _wino1d_cl / _bf16_cl), of smos_stem_gemm, of
- * smos_pointnet_scatter / _rows / _rows_live, of smos_gather_scatter_cl / _live / _view and of the emit, copy, start and sum
+ * smos_pointnet_scatter / _rows, of smos_gather_scatter_cl and of the emit, copy, start and sum
  * kernels of smos_bilinear_gather_bwd_det / smos_msda_bwd_det and of smos_train_prep_build / _draws and smos_copy_paste_* at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
  * item-boundary code paths, a wave's whole-tile / head / tail units of the stem, the scatter's software pipeline -- on shapes
  * small enough to check against float64.  The results do not depend on it. */
@@ -463,39 +463,33 @@ int smos_upconv_ypass(const float* conv_a, int64_t a_pitch, const float* bias, c
  *   A2[(mt*48 + s)*64 + lane] = W2[mt*32 + (lane&31)][ch(s, lane>>5)],  A3[s*64 + lane] = W3[lane&31][ch(s, lane>>5)] (0 beyond M3)
  *   with ch(s, h) = 32 (s >> 4) + 8 ((s & 15) >> 2) + 4 h + (s & 3)   (the accumulator order of the previous layer). */
 int64_t smos_point_head_weight_floats(void);
-int smos_point_head(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N, int64_t K1,
-                    int64_t M1, int64_t M2, int64_t M3, smos_stream_t stream);
-/* The same with the scan's padding tail left out: n_live (DEVICE int32, may be NULL = no tail) says how many points at the
+/* The scan's padding tail can be left out: n_live (DEVICE int32, may be NULL = no tail) says how many points at the
  * front of every sample are real -- the reference pads every scan to frame_point_num with points at -1000
  * (datasets/data_StreamMOS.py:568-571) and cuts their predictions off again (val_StreamMOS.py:113); the logits of points
- * [*n_live, N) are written as zeros without being computed.  The streaming runner's form; AttNet.infer computes all N. */
-int smos_point_head_live(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N, int64_t K1,
-                         int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, smos_stream_t stream);
+ * [*n_live, N) are written as zeros without being computed.  The streaming runner passes a count; AttNet.infer computes all N. */
+int smos_point_head(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N, int64_t K1,
+                    int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, smos_stream_t stream);
 
-/* smos_point_head_live with the middle 64-channel segment of every row gathered from a channels-last map instead of read from
+/* smos_point_head with the middle 64-channel segment of every row gathered from a channels-last map instead of read from
  * the row: channel 64 + c of point (b, n) = BilinearSample of grid [B, Hg, Wg, *] (pixel pitch grid_pitch floats, channels
  * [0, 64) read, 16-byte aligned, < 2 GiB) at gcoord * gscale, with the position arithmetic, tap order and absent-tap rule of
- * smos_gather_scatter_cl_view (gcoord, Kg, g_batch_stride, gscale as there).  Floats [64, 128) of `rows` are neither read nor
- * written; the logits equal those of smos_gather_scatter_cl_view(pts_out = rows + 64) followed by smos_point_head_live bit
+ * smos_gather_scatter_cl (gcoord, Kg, g_batch_stride, gscale as there).  Floats [64, 128) of `rows` are neither read nor
+ * written; the logits equal those of smos_gather_scatter_cl(pts_out = rows + 64) followed by smos_point_head bit
  * for bit.  Replaces networks/backbone.py:453-475 (bev_grid2point) + :387-413,188-196 of the decoder's tail in one launch. */
-int smos_point_head_gather_live(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N,
-                                int64_t K1, int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, const float* grid,
-                                int64_t grid_pitch, int64_t Hg, int64_t Wg, const float* gcoord, int32_t Kg,
-                                int64_t g_batch_stride, const float* gscale, smos_stream_t stream);
+int smos_point_head_gather(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N,
+                           int64_t K1, int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, const float* grid,
+                           int64_t grid_pitch, int64_t Hg, int64_t Wg, const float* gcoord, int32_t Kg,
+                           int64_t g_batch_stride, const float* gscale, smos_stream_t stream);
 
 /* smos_pointnet_scatter with a COMPACT target: rows [n_rows, T*cout] (zero-filled by smos_stem_scan) instead of
- * the dense [B,H,W,T*cout] grid; the features of cell (b, y, x) go to row row_of[b][y][x] (smos_stem_scan). */
+ * the dense [B,H,W,T*cout] grid; the features of cell (b, y, x) go to row row_of[b][y][x] (smos_stem_scan).
+ * It can be told how many points of the current scan are real (n_live: DEVICE int32 or NULL; see smos_point_head): the point
+ * rows of the padding tail [*n_live, N) are not computed and not written.  The scatter itself is unaffected (padding points lie
+ * outside the grid). */
 int smos_pointnet_scatter_rows(const float* xyzi, const float* coord, int32_t K, const float* w1, const float* b1,
                                const float* w2, const float* b2, float* rows, const int32_t* row_of, float* pts_out,
                                int64_t po_b, int64_t po_n, int64_t B, int64_t T, int64_t N, int64_t H, int64_t W, int32_t cin,
-                               int32_t cmid, int32_t cout, smos_stream_t stream);
-/* The same, told how many points of the current scan are real (n_live: DEVICE int32 or NULL; see smos_point_head_live): the point
- * rows of the padding tail [*n_live, N) are not computed and not written.  The scatter itself is unaffected (padding points lie
- * outside the grid). */
-int smos_pointnet_scatter_rows_live(const float* xyzi, const float* coord, int32_t K, const float* w1, const float* b1,
-                                    const float* w2, const float* b2, float* rows, const int32_t* row_of, float* pts_out,
-                                    int64_t po_b, int64_t po_n, int64_t B, int64_t T, int64_t N, int64_t H, int64_t W, int32_t cin,
-                                    int32_t cmid, int32_t cout, const int32_t* n_live, smos_stream_t stream);
+                               int32_t cmid, int32_t cout, const int32_t* n_live, smos_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * Device-side validation preprocessing (csrc/preprocess.hip): what DataloadVal does with
@@ -690,24 +684,16 @@ int smos_downsample_pool_branch(const float* x, int64_t x_pitch, const float* wp
 /* BilinearSample (networks/backbone.py:453-475) of the channels-last grid [B,Hg,Wg,*] (pixel pitch grid_pitch, C channels read)
  * at gcoord*gscale, fused with VoxelMaxPool of the result into the zero-filled channels-last out [B,Ho,Wo,*] (pixel pitch
  * out_pitch) at int(scoord*sscale) (networks/multi_view_encoder.py:395-404,410-419).  out may be NULL (gather only); pts_out
- * (optional) receives the gathered features as rows pts_out[b*po_b + n*po_n + c].  C is 32 or 64. */
-int smos_gather_scatter_cl(const float* grid, int64_t grid_pitch, const float* gcoord, int32_t Kg, const float* gscale,
-                           const float* scoord, int32_t Ks, const float* sscale, float* out, int64_t out_pitch, float* pts_out,
-                           int64_t po_b, int64_t po_n, int64_t B, int64_t C, int64_t Hg, int64_t Wg, int64_t N, int64_t Ho,
-                           int64_t Wo, smos_stream_t stream);
-/* The same with n_live (DEVICE int32 or NULL; see smos_point_head_live): point rows of the padding tail are not written. */
-int smos_gather_scatter_cl_live(const float* grid, int64_t grid_pitch, const float* gcoord, int32_t Kg, const float* gscale,
-                                const float* scoord, int32_t Ks, const float* sscale, float* out, int64_t out_pitch, float* pts_out,
-                                int64_t po_b, int64_t po_n, int64_t B, int64_t C, int64_t Hg, int64_t Wg, int64_t N, int64_t Ho,
-                                int64_t Wo, const int32_t* n_live, smos_stream_t stream);
-/* The same with the coordinates as strided views: sample b, point n at coord + b * batch_stride + n * K floats (the first two
- * of a point's K values are read).  Lets a caller pass pcds_coord[:, 0, :, :, 0] of the reference's [B, T, N, 3, 1] tensor
- * (networks/multi_view_encoder.py:395-420 slice it the same way) without a compacting copy. */
-int smos_gather_scatter_cl_view(const float* grid, int64_t grid_pitch, const float* gcoord, int32_t Kg, int64_t g_batch_stride,
-                                const float* gscale, const float* scoord, int32_t Ks, int64_t s_batch_stride, const float* sscale,
-                                float* out, int64_t out_pitch, float* pts_out, int64_t po_b, int64_t po_n, int64_t B, int64_t C,
-                                int64_t Hg, int64_t Wg, int64_t N, int64_t Ho, int64_t Wo, const int32_t* n_live,
-                                smos_stream_t stream);
+ * (optional) receives the gathered features as rows pts_out[b*po_b + n*po_n + c].  C is 32 or 64.
+ * n_live (DEVICE int32 or NULL; see smos_point_head): point rows of the padding tail are not written.
+ * The coordinates are strided views: sample b, point n at coord + b * batch_stride + n * K floats (the first two of a point's
+ * K values are read; a dense [B, N, K] tensor has batch_stride N * K).  Lets a caller pass pcds_coord[:, 0, :, :, 0] of the
+ * reference's [B, T, N, 3, 1] tensor (networks/multi_view_encoder.py:395-420 slice it the same way) without a compacting copy. */
+int smos_gather_scatter_cl(const float* grid, int64_t grid_pitch, const float* gcoord, int32_t Kg, int64_t g_batch_stride,
+                           const float* gscale, const float* scoord, int32_t Ks, int64_t s_batch_stride, const float* sscale,
+                           float* out, int64_t out_pitch, float* pts_out, int64_t po_b, int64_t po_n, int64_t B, int64_t C,
+                           int64_t Hg, int64_t Wg, int64_t N, int64_t Ho, int64_t Wo, const int32_t* n_live,
+                           smos_stream_t stream);
 
 /* Per-frame label outputs of the overlapped sequence loop (streammos_amd/run_sequence.py).  labels [n] uint8 in {0,1,2}
  * (4-byte aligned) -> words [n] int32 (16-byte aligned; NULL: not written): lut != 0 the learning_map_inv value 0 / 9 / 251

@@ -53,12 +53,10 @@ SIGNATURES = {
     "smos_stem_scan": [vp, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp],
     "smos_stem_gemm": [vp, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), i64, i64, vp],
     "smos_stem_epilogue": [ctypes.POINTER(vp), vp, vp, vp, vp, i64, i64, i64, i64, i64, vp],
-    "smos_pointnet_scatter_rows": [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, i32, i32, vp],
-    "smos_pointnet_scatter_rows_live": [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, i32, i32, vp, vp],
+    "smos_pointnet_scatter_rows": [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, i32, i32, i32, vp, vp],
     "smos_point_head_weight_floats": [],
-    "smos_point_head": [vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, vp],
-    "smos_point_head_live": [vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp],
-    "smos_point_head_gather_live": [vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, vp, i32, i64, c_f32p, vp],
+    "smos_point_head": [vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp],
+    "smos_point_head_gather": [vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, i64, i64, i64, vp, i32, i64, c_f32p, vp],
     "smos_conv_cl_sum_chunks": [i64, i64],
     "smos_conv_cl": [vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp],
     "smos_conv_rows_cl": [vp, i64, vp, vp, vp, i64, vp, i64, i64, i64, i64, i64, i64, i32, i32, i32, i32, vp, vp],
@@ -103,10 +101,8 @@ SIGNATURES = {
     "smos_channel_gate_residual_cl": [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, vp],
     "smos_channel_gate_apply_cl": [vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, i64, i64, i64, vp],
     "smos_upsample_concat_cl": [ctypes.POINTER(vp), c_i64p, c_i64p, c_i64p, c_i64p, i32, vp, i64, i64, i64, vp],
-    "smos_gather_scatter_cl": [vp, i64, vp, i32, c_f32p, vp, i32, c_f32p, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp],
     "smos_downsample_pool_branch": [vp, i64, vp, vp, i64, vp, vp, i64, i64, i64, i64, i64, i64, i32, vp],
-    "smos_gather_scatter_cl_view": [vp, i64, vp, i32, i64, c_f32p, vp, i32, i64, c_f32p, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp],
-    "smos_gather_scatter_cl_live": [vp, i64, vp, i32, c_f32p, vp, i32, c_f32p, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp],
+    "smos_gather_scatter_cl": [vp, i64, vp, i32, i64, c_f32p, vp, i32, i64, c_f32p, vp, i64, vp, i64, i64, i64, i64, i64, i64, i64, i64, i64, vp, vp],
     "smos_label_words": [vp, i64, i32, vp, vp, vp, i32, vp, vp],
     "smos_label_count_voted": [vp, i64, vp, vp, vp, i32, vp, vp],
     "smos_point_mlp_chunk": [],
@@ -117,7 +113,15 @@ SIGNATURES = {
     "smos_point_mlp_bwd": [vp, vp, i64, i64, i32, ctypes.POINTER(vp), c_f64p, vp, vp, ctypes.POINTER(vp), vp, i64, vp],
 }
 
-ABI_VERSION = 1      # SMOS_ABI_VERSION of the include/smos.h these signatures were written against
+# the entries that return int64_t; every other one returns int (a status, or a small count)
+INT64_RESULTS = (
+    "smos_bilinear_gather_bwd_det_work_bytes", "smos_seg_loss_work_bytes", "smos_msda_bwd_det_work_bytes", "smos_dbscan_work_bytes",
+    "smos_instance_work_bytes", "smos_stem_scan_state_words", "smos_point_head_weight_floats", "smos_conv_cl_sum_chunks",
+    "smos_conv_wino_sum_chunks", "smos_basic_block_ws_floats", "smos_tfusion_layer_param_floats", "smos_tfusion_layer_stream_floats",
+    "smos_train_prep_work_bytes", "smos_copy_paste_work_bytes", "smos_point_mlp_work_bytes",
+)
+
+ABI_VERSION = 2      # SMOS_ABI_VERSION of the include/smos.h these signatures were written against
 
 _lib = None
 
@@ -152,22 +156,7 @@ def load():
             raise RuntimeError("streammos_amd: %s has no %s -- it was built from an older tree; rebuild it "
                                "(`python -m streammos_amd.build -f`)" % (LIB_PATH, name))
         fn.argtypes = argtypes
-        fn.restype = ctypes.c_int
-    lib.smos_dbscan_work_bytes.restype = ctypes.c_int64
-    lib.smos_instance_work_bytes.restype = ctypes.c_int64
-    lib.smos_stem_scan_state_words.restype = ctypes.c_int64
-    lib.smos_seg_loss_work_bytes.restype = ctypes.c_int64
-    lib.smos_bilinear_gather_bwd_det_work_bytes.restype = ctypes.c_int64
-    lib.smos_msda_bwd_det_work_bytes.restype = ctypes.c_int64
-    lib.smos_train_prep_work_bytes.restype = ctypes.c_int64
-    lib.smos_copy_paste_work_bytes.restype = ctypes.c_int64
-    lib.smos_point_mlp_work_bytes.restype = ctypes.c_int64
-    lib.smos_conv_cl_sum_chunks.restype = ctypes.c_int64
-    lib.smos_conv_wino_sum_chunks.restype = ctypes.c_int64
-    lib.smos_basic_block_ws_floats.restype = ctypes.c_int64
-    lib.smos_point_head_weight_floats.restype = ctypes.c_int64
-    lib.smos_tfusion_layer_param_floats.restype = ctypes.c_int64
-    lib.smos_tfusion_layer_stream_floats.restype = ctypes.c_int64
+        fn.restype = ctypes.c_int64 if name in INT64_RESULTS else ctypes.c_int
     lib.smos_last_error.argtypes = []
     lib.smos_last_error.restype = ctypes.c_char_p
     _lib = lib
@@ -178,6 +167,24 @@ def check(rc, what):
     if rc != 0:
         msg = load().smos_last_error().decode(errors="replace")
         raise RuntimeError("%s failed (smos status %d): %s" % (what, rc, msg))
+
+
+def entry(name):
+    """The bound entry `name` of the loaded library, for the one caller that makes the foreign call itself (ops._conv_launch:
+    a Python-level ``call`` costs it 0.1 - 0.25 us per launch, profiles/abi_boundary.txt)."""
+    return getattr(_lib or load(), name)
+
+
+def call(name, *args):
+    """Calls the entry `name` of the loaded library; a non-zero status raises the RuntimeError of ``check``."""
+    rc = getattr(_lib or load(), name)(*args)
+    if rc:
+        check(rc, name)
+
+
+def query(name, *args):
+    """The number a value query returns (``*_work_bytes``, ``*_floats``, ``*_chunk``, ``*_ok``, ...): no status to check."""
+    return int(getattr(_lib or load(), name)(*args))
 
 
 def i64_array(values):

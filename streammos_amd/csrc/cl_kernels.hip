@@ -636,38 +636,16 @@ extern "C" int smos_upsample_concat_cl(const float* const* src, const int64_t* s
   return check_launch("upsample_concat_cl");
 }
 
-extern "C" int smos_gather_scatter_cl_view(const float* grid, int64_t grid_pitch, const float* gcoord, int32_t Kg, int64_t g_batch_stride,
-                                           const float* gscale, const float* scoord, int32_t Ks, int64_t s_batch_stride,
-                                           const float* sscale, float* out, int64_t out_pitch, float* pts_out, int64_t po_b,
-                                           int64_t po_n, int64_t B, int64_t C, int64_t Hg, int64_t Wg, int64_t N, int64_t Ho,
-                                           int64_t Wo, const int32_t* n_live, smos_stream_t stream);
-
-extern "C" int smos_gather_scatter_cl(const float* grid, int64_t grid_pitch, const float* gcoord, int32_t Kg, const float* gscale,
-                                      const float* scoord, int32_t Ks, const float* sscale, float* out, int64_t out_pitch,
-                                      float* pts_out, int64_t po_b, int64_t po_n, int64_t B, int64_t C, int64_t Hg, int64_t Wg,
-                                      int64_t N, int64_t Ho, int64_t Wo, smos_stream_t stream) {
-  return smos_gather_scatter_cl_live(grid, grid_pitch, gcoord, Kg, gscale, scoord, Ks, sscale, out, out_pitch, pts_out, po_b, po_n, B, C,
-                                     Hg, Wg, N, Ho, Wo, nullptr, stream);
-}
-
 // n_live (device int32, may be null): the first *n_live points of every sample are real; point rows of the padding tail that lie
-// wholly outside the source map are not written (they would be zeros nobody reads).  Everything else as smos_gather_scatter_cl.
-extern "C" int smos_gather_scatter_cl_live(const float* grid, int64_t grid_pitch, const float* gcoord, int32_t Kg, const float* gscale,
-                                           const float* scoord, int32_t Ks, const float* sscale, float* out, int64_t out_pitch,
-                                           float* pts_out, int64_t po_b, int64_t po_n, int64_t B, int64_t C, int64_t Hg, int64_t Wg,
-                                           int64_t N, int64_t Ho, int64_t Wo, const int32_t* n_live, smos_stream_t stream) {
-  return smos_gather_scatter_cl_view(grid, grid_pitch, gcoord, Kg, N * Kg, gscale, scoord, Ks, N * Ks, sscale, out, out_pitch, pts_out,
-                                     po_b, po_n, B, C, Hg, Wg, N, Ho, Wo, n_live, stream);
-}
-
-// The coordinates as strided views: sample b, point n at coord + b * batch_stride + n * K (floats; the first two of a point's K
+// wholly outside the source map are not written (they would be zeros nobody reads).
+// The coordinates are strided views: sample b, point n at coord + b * batch_stride + n * K (floats; the first two of a point's K
 // values are read) -- the engine passes pcds_coord[:, 0, :, :, 0] of the reference's [B, T, N, 3, 1] tensor as it lies, without a
-// compacting copy.  Everything else as smos_gather_scatter_cl_live.
-extern "C" int smos_gather_scatter_cl_view(const float* grid, int64_t grid_pitch, const float* gcoord, int32_t Kg, int64_t g_batch_stride,
-                                           const float* gscale, const float* scoord, int32_t Ks, int64_t s_batch_stride,
-                                           const float* sscale, float* out, int64_t out_pitch, float* pts_out, int64_t po_b,
-                                           int64_t po_n, int64_t B, int64_t C, int64_t Hg, int64_t Wg, int64_t N, int64_t Ho,
-                                           int64_t Wo, const int32_t* n_live, smos_stream_t stream) {
+// compacting copy.
+extern "C" int smos_gather_scatter_cl(const float* grid, int64_t grid_pitch, const float* gcoord, int32_t Kg, int64_t g_batch_stride,
+                                      const float* gscale, const float* scoord, int32_t Ks, int64_t s_batch_stride,
+                                      const float* sscale, float* out, int64_t out_pitch, float* pts_out, int64_t po_b,
+                                      int64_t po_n, int64_t B, int64_t C, int64_t Hg, int64_t Wg, int64_t N, int64_t Ho,
+                                      int64_t Wo, const int32_t* n_live, smos_stream_t stream) {
   SMOS_REQUIRE(B > 0 && (C == 32 || C == 64) && N > 0 && Hg > 0 && Wg > 0 && Kg >= 2, "gather_scatter_cl: bad sizes (C must be 32 or 64)");
   SMOS_REQUIRE(g_batch_stride >= 0 && (!out || s_batch_stride >= 0), "gather_scatter_cl: negative coordinate stride");
   SMOS_REQUIRE(grid && gcoord && gscale && (out || pts_out) && grid_pitch >= C, "gather_scatter_cl: null pointer / bad pitch");

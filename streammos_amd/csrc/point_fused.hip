@@ -311,21 +311,12 @@ extern "C" int smos_pointnet_scatter(const float* xyzi, const float* coord, int3
                                  cout, stream);
 }
 
+// n_live (device int32, may be null): the first *n_live points of the current (t == 0) scan of every sample are real; the point
+// rows of its padding tail are not written (nothing reads them once the point head knows the same count).
 extern "C" int smos_pointnet_scatter_rows(const float* xyzi, const float* coord, int32_t K, const float* w1, const float* b1,
                                           const float* w2, const float* b2, float* rows, const int32_t* row_of, float* pts_out,
                                           int64_t po_b, int64_t po_n, int64_t B, int64_t T, int64_t N, int64_t H, int64_t W,
-                                          int32_t cin, int32_t cmid, int32_t cout, smos_stream_t stream) {
-  SMOS_REQUIRE(row_of, "pointnet_scatter_rows: null row table");
-  return pointnet_scatter_launch(xyzi, coord, K, w1, b1, w2, b2, rows, row_of, pts_out, nullptr, po_b, po_n, B, T, N, H, W, cin, cmid,
-                                 cout, stream);
-}
-
-// n_live (device int32, may be null): the first *n_live points of the current (t == 0) scan of every sample are real; the point
-// rows of its padding tail are not written (nothing reads them once the point head knows the same count).
-extern "C" int smos_pointnet_scatter_rows_live(const float* xyzi, const float* coord, int32_t K, const float* w1, const float* b1,
-                                               const float* w2, const float* b2, float* rows, const int32_t* row_of, float* pts_out,
-                                               int64_t po_b, int64_t po_n, int64_t B, int64_t T, int64_t N, int64_t H, int64_t W,
-                                               int32_t cin, int32_t cmid, int32_t cout, const int32_t* n_live, smos_stream_t stream) {
+                                          int32_t cin, int32_t cmid, int32_t cout, const int32_t* n_live, smos_stream_t stream) {
   SMOS_REQUIRE(row_of, "pointnet_scatter_rows: null row table");
   return pointnet_scatter_launch(xyzi, coord, K, w1, b1, w2, b2, rows, row_of, pts_out, n_live, po_b, po_n, B, T, N, H, W, cin, cmid,
                                  cout, stream);

@@ -10,7 +10,7 @@
 //   layer 2 / 3 walk their input channels in accumulator order: register r of tile mt, lane half h = channel
 //   32 mt + 8 (r >> 2) + 4 h + (r & 3).
 // Output: logits [B, M3, N] (the reference's (B, 3, N, 1) layout), 32 contiguous floats per channel and tile.
-// point_head<true> (smos_point_head_gather_live) builds the middle third itself: the decoder's grid -> point bilinear gather
+// point_head<true> (smos_point_head_gather) builds the middle third itself: the decoder's grid -> point bilinear gather
 // (gather_scatter_cl4 without a scatter target) with the position arithmetic and the tap sum of smos_common.h, so the logits
 // equal those of the gather launch followed by point_head<false> bit for bit, and nobody writes or reads the BEV third of the
 // rows.  The 32 tap loads of a lane are requested behind the first third's row loads and summed behind its MFMAs.
@@ -39,7 +39,7 @@ struct HeadArgs {
   const int32_t* n_live; // device: points [*n_live, N) of every sample are the padding tail of the scan (null: none)
   int64_t rp;
   int B, N, M3;
-  // point_head<true> only: the channels-last map the middle third is gathered from, as smos_gather_scatter_cl_view takes it
+  // point_head<true> only: the channels-last map the middle third is gathered from, as smos_gather_scatter_cl takes it
   const float* grid;     // [B, Hg, Wg, *] pixel pitch gp floats (channel offset applied), 64 channels read
   const float* gcoord;   // sample b, point n at gcoord + b * gbs + n * Kg
   int64_t gp, gbs;
@@ -251,30 +251,22 @@ static int launch_point_head(HeadArgs a, int64_t K1, int64_t M1, int64_t M2, smo
 
 static bool fits_int(int64_t v) { return v > 0 && v < (1LL << 31); }
 
-extern "C" int smos_point_head_live(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N,
-                                    int64_t K1, int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, smos_stream_t stream);
-
-extern "C" int smos_point_head(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N,
-                               int64_t K1, int64_t M1, int64_t M2, int64_t M3, smos_stream_t stream) {
-  return smos_point_head_live(rows, row_pitch, wprep, out, B, N, K1, M1, M2, M3, nullptr, stream);
-}
-
 // n_live (device int32, may be null): the first *n_live points of every sample are real, the rest is the scan's padding tail,
 // whose logits are written as zeros without being computed.
-extern "C" int smos_point_head_live(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N,
-                                    int64_t K1, int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, smos_stream_t stream) {
+extern "C" int smos_point_head(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N,
+                               int64_t K1, int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, smos_stream_t stream) {
   SMOS_REQUIRE(fits_int(B) && fits_int(N) && M3 <= 32, "point_head: bad sizes");
   HeadArgs a = {};
   a.rows = rows; a.wprep = wprep; a.out = out; a.n_live = n_live; a.rp = row_pitch; a.B = (int)B; a.N = (int)N; a.M3 = (int)M3;
   return launch_point_head<false>(a, K1, M1, M2, stream);
 }
 
-// The same with channels [64, 128) of every row taken from `grid` by the bilinear gather of smos_gather_scatter_cl_view instead
+// The same with channels [64, 128) of every row taken from `grid` by the bilinear gather of smos_gather_scatter_cl instead
 // of from the row: floats [64, 128) of `rows` are neither read nor written.
-extern "C" int smos_point_head_gather_live(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N,
-                                           int64_t K1, int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, const float* grid,
-                                           int64_t grid_pitch, int64_t Hg, int64_t Wg, const float* gcoord, int32_t Kg,
-                                           int64_t g_batch_stride, const float* gscale, smos_stream_t stream) {
+extern "C" int smos_point_head_gather(const float* rows, int64_t row_pitch, const float* wprep, float* out, int64_t B, int64_t N,
+                                      int64_t K1, int64_t M1, int64_t M2, int64_t M3, const int32_t* n_live, const float* grid,
+                                      int64_t grid_pitch, int64_t Hg, int64_t Wg, const float* gcoord, int32_t Kg,
+                                      int64_t g_batch_stride, const float* gscale, smos_stream_t stream) {
   SMOS_REQUIRE(fits_int(B) && fits_int(N) && M3 <= 32, "point_head: bad sizes");
   SMOS_REQUIRE(grid && gcoord && gscale && (reinterpret_cast<uintptr_t>(grid) & 15) == 0 && grid_pitch >= 64 && grid_pitch % 4 == 0,
                "point_head_gather: null / unaligned grid or bad pitch (64 channels are read)");

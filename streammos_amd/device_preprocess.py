@@ -49,7 +49,6 @@ class DevicePreprocessor:
         of bounds -- surplus points are dropped -- and the per-scan in-range counts stay on the device in
         ``in_range_counts``; ``check_capacity`` turns them into the host path's error.  strict=True checks at once
         (one stream synchronisation); the streaming runner checks when it reads the labels back anyway."""
-        lib = _lib.load()
         T, N, V = len(scans), self.N, self.V
         dev = self.device
         xyzi = torch.empty((V, T, 7, N, 1), dtype=torch.float32, device=dev)
@@ -68,12 +67,11 @@ class DevicePreprocessor:
                 pd = None
                 if pose is not None and not np.array_equal(np.asarray(pose), np.eye(4)):
                     pd = _lib.f64_array(np.asarray(pose, dtype=np.float64).reshape(-1)[:16])
-                _lib.check(lib.smos_prep_transform_mask(scan.data_ptr(), n, pd, self._range6, moved.data_ptr(), mask.data_ptr(),
-                                                        stream), "smos_prep_transform_mask")
+                _lib.call("smos_prep_transform_mask", scan.data_ptr(), n, pd, self._range6, moved.data_ptr(), mask.data_ptr(),
+                          stream)
                 prefix = torch.cumsum(mask, 0, dtype=torch.int32)
-                _lib.check(lib.smos_prep_emit(moved.data_ptr(), mask.data_ptr(), prefix.data_ptr(), n, t, T, N, V, self._sx,
-                                              self._sy, self._range6, self._bev3, self._rv4, xyzi.data_ptr(), coord.data_ptr(),
-                                              sphere.data_ptr(), stream), "smos_prep_emit")
+                _lib.call("smos_prep_emit", moved.data_ptr(), mask.data_ptr(), prefix.data_ptr(), n, t, T, N, V, self._sx, self._sy,
+                          self._range6, self._bev3, self._rv4, xyzi.data_ptr(), coord.data_ptr(), sphere.data_ptr(), stream)
                 if n > 0:
                     counts[t:t + 1].copy_(prefix[-1:])
                 if t == 0:
@@ -90,12 +88,11 @@ class DevicePreprocessor:
 
     def unpad_labels(self, labels, built):
         """labels [N] uint8 of the padded sample -> [n_raw] uint8 for the raw scan (0 where out of range)."""
-        lib = _lib.load()
         raw = torch.empty(built["n_raw"], dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(lib.smos_prep_unpad_labels(labels.data_ptr(), labels.shape[0], built["mask"].data_ptr(),
-                                                  built["prefix"].data_ptr(), built["n_raw"], raw.data_ptr(),
-                                                  torch.cuda.current_stream(self.device).cuda_stream), "smos_prep_unpad_labels")
+            _lib.call("smos_prep_unpad_labels", labels.data_ptr(), labels.shape[0], built["mask"].data_ptr(),
+                      built["prefix"].data_ptr(), built["n_raw"], raw.data_ptr(),
+                      torch.cuda.current_stream(self.device).cuda_stream)
         return raw
 
 
@@ -242,13 +239,11 @@ class DeviceTrainPreprocessor(_RowStaging):
         """The draws ``build(seed=seed, sample_index=sample_index)`` uses, as explicit ``TrainDraws`` with device tensors:
         smos_train_prep_draws for the words and the noise, ``preprocess.seeded_scalars`` for the five scalars."""
         seed, sample_index = self._check_seed(seed, sample_index)
-        lib = _lib.load()
         words = torch.empty((self.W, self.T, self.N), dtype=torch.int32, device=self.device)
         noise = torch.empty((self.W, self.T * self.N, 3), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(lib.smos_train_prep_draws(seed, sample_index, self.N, float(self.aug.noise_mean), float(self.aug.noise_std),
-                                                 words.data_ptr(), noise.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream),
-                       "smos_train_prep_draws")
+            _lib.call("smos_train_prep_draws", seed, sample_index, self.N, float(self.aug.noise_mean), float(self.aug.noise_std),
+                      words.data_ptr(), noise.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
         return preprocess.TrainDraws(words, noise, *preprocess.seeded_scalars(seed, sample_index, self.aug))
 
     @staticmethod
@@ -268,7 +263,6 @@ class DeviceTrainPreprocessor(_RowStaging):
         aligned=True: the scans already went through the first alignment (the state in which the reference's copy-paste
         augmentation edits them); only the windows' second alignment is applied.
         Every argument is checked before the first launch; an argument error is a RuntimeError."""
-        lib = _lib.load()
         if (draws is None) == (seed is None):
             raise RuntimeError("DeviceTrainPreprocessor.build: give either draws or seed, not both and not neither")
         if len(scans) != preprocess.TRAIN_FRAMES or len(label_words) != preprocess.TRAIN_FRAMES:
@@ -313,7 +307,7 @@ class DeviceTrainPreprocessor(_RowStaging):
                 shift, scale, h_flip, v_flip, theta_z = preprocess.seeded_scalars(seed, sample_index, self.aug)
             scan_ptrs, lengths, keep_s = self._device_rows(scans, torch.float32, (4,))
             word_ptrs, _, keep_w = self._device_rows(label_words, torch.int32, ())
-            work_bytes = lib.smos_train_prep_work_bytes(max(lengths))
+            work_bytes = _lib.query("smos_train_prep_work_bytes", max(lengths))
             if work_bytes < 0:
                 raise RuntimeError("DeviceTrainPreprocessor: a scan of %d points is too large" % max(lengths))
             work = self._work.get(stream.cuda_stream)
@@ -326,16 +320,15 @@ class DeviceTrainPreprocessor(_RowStaging):
             vp5, vp3 = ctypes.c_void_p * preprocess.TRAIN_FRAMES, ctypes.c_void_p * W
             targets = (ctypes.c_void_p * (len(self.target_names) * W))(
                 *[slices["%s_%d" % (name, w)].data_ptr() for name in self.target_names for w in range(W)])
-            _lib.check(lib.smos_train_prep_build(
-                vp5(*scan_ptrs), vp5(*word_ptrs), _lib.i64_array(lengths), _lib.f64_array(first), _lib.f64_array(second), self._range6,
-                self._bev3, self._rv4, N, words_ptr, noise_ptr, seed, sample_index, float(self.aug.noise_mean), float(self.aug.noise_std),
-                _lib.f64_array(shift), float(scale), int(v_flip), int(h_flip), float(np.cos(ang)), float(np.sin(ang)),
-                self._lut.data_ptr(), len(self.target_names), self._lut.shape[1],
-                vp3(*[slices["pcds_xyzi_%d" % w].data_ptr() for w in range(W)]),
-                vp3(*[slices["pcds_coord_%d" % w].data_ptr() for w in range(W)]),
-                vp3(*[slices["pcds_sphere_coord_%d" % w].data_ptr() for w in range(W)]), targets,
-                vp3(*[slices["pcds_bev_target_%d" % w].data_ptr() for w in range(W)]), slices["in_range_counts"].data_ptr(),
-                work.data_ptr(), work.numel(), stream.cuda_stream), "smos_train_prep_build")
+            _lib.call("smos_train_prep_build", vp5(*scan_ptrs), vp5(*word_ptrs), _lib.i64_array(lengths), _lib.f64_array(first),
+                      _lib.f64_array(second), self._range6, self._bev3, self._rv4, N, words_ptr, noise_ptr, seed, sample_index,
+                      float(self.aug.noise_mean), float(self.aug.noise_std), _lib.f64_array(shift), float(scale), int(v_flip),
+                      int(h_flip), float(np.cos(ang)), float(np.sin(ang)), self._lut.data_ptr(), len(self.target_names),
+                      self._lut.shape[1], vp3(*[slices["pcds_xyzi_%d" % w].data_ptr() for w in range(W)]),
+                      vp3(*[slices["pcds_coord_%d" % w].data_ptr() for w in range(W)]),
+                      vp3(*[slices["pcds_sphere_coord_%d" % w].data_ptr() for w in range(W)]), targets,
+                      vp3(*[slices["pcds_bev_target_%d" % w].data_ptr() for w in range(W)]), slices["in_range_counts"].data_ptr(),
+                      work.data_ptr(), work.numel(), stream.cuda_stream)
             for t in keep_s + keep_w + ([words, noise] if draws is not None else []):   # read by the launches above
                 t.record_stream(stream)
         return out
@@ -493,14 +486,13 @@ class DeviceCopyPaste(_RowStaging):
         """The draws ``apply(seed=seed, sample_index=sample_index)`` uses, as explicit ``PasteDraws`` with device noise:
         ``preprocess.seeded_paste_scalars`` for the host scalars, smos_copy_paste_draws for the noise."""
         seed, sample_index = DeviceTrainPreprocessor._check_seed(seed, sample_index)
-        lib = _lib.load()
         index, velocity, order = preprocess.seeded_paste_scalars(seed, sample_index, self.bank.categories, self.max_objects)
         noise = []
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             for i, b in enumerate(index):
                 nz = torch.empty((preprocess.TRAIN_FRAMES, self.bank.sizes[b], 3), dtype=torch.float64, device=self.device)
-                _lib.check(lib.smos_copy_paste_draws(seed, sample_index, i, self.bank.sizes[b], nz.data_ptr(), stream), "smos_copy_paste_draws")
+                _lib.call("smos_copy_paste_draws", seed, sample_index, i, self.bank.sizes[b], nz.data_ptr(), stream)
                 noise.append(nz)
         return preprocess.PasteDraws(index, velocity, order, noise)
 
@@ -511,7 +503,6 @@ class DeviceCopyPaste(_RowStaging):
         layout (M = the points of all drawn objects; views of one allocation each) -- first-aligned, to be built with
         aligned=True -- and status [count] int32 on the device: the accepted trial of each object or -1.
         Every argument is checked before the first launch; an argument error is a RuntimeError."""
-        lib = _lib.load()
         if (draws is None) == (seed is None):
             raise RuntimeError("DeviceCopyPaste.apply: give either draws or seed, not both and not neither")
         F = preprocess.TRAIN_FRAMES
@@ -544,7 +535,7 @@ class DeviceCopyPaste(_RowStaging):
             stream = torch.cuda.current_stream(self.device)
             scan_ptrs, lengths, keep_s = self._device_rows(scans, torch.float32, (4,))
             word_ptrs, _, keep_w = self._device_rows(label_words, torch.int32, ())
-            work_bytes = lib.smos_copy_paste_work_bytes(lengths[0])
+            work_bytes = _lib.query("smos_copy_paste_work_bytes", lengths[0])
             if work_bytes < 0:
                 raise RuntimeError("DeviceCopyPaste: a scan of %d points is too large" % lengths[0])
             work = self._work.get(stream.cuda_stream)
@@ -561,9 +552,9 @@ class DeviceCopyPaste(_RowStaging):
             first = np.stack([inv0.dot(p) for p in poses])
             vp5 = ctypes.c_void_p * F
             n5 = _lib.i64_array(lengths)
-            _lib.check(lib.smos_copy_paste_begin(vp5(*scan_ptrs), vp5(*word_ptrs), n5, _lib.f64_array(first.reshape(-1)), slots, draws.count,
-                                                 pts.data_ptr(), words.data_ptr(), ang.data_ptr(), flags.data_ptr(), status.data_ptr(),
-                                                 stream.cuda_stream), "smos_copy_paste_begin")
+            _lib.call("smos_copy_paste_begin", vp5(*scan_ptrs), vp5(*word_ptrs), n5, _lib.f64_array(first.reshape(-1)), slots,
+                      draws.count, pts.data_ptr(), words.data_ptr(), ang.data_ptr(), flags.data_ptr(), status.data_ptr(),
+                      stream.cuda_stream)
             first0 = _lib.f64_array(first[0].reshape(-1))
             keep_n, slot = [], 0
             for i, b in enumerate(draws.index):
@@ -578,14 +569,14 @@ class DeviceCopyPaste(_RowStaging):
                     nz = self._stage([np.ascontiguousarray(nz)], torch.float64)
                 if nz is not None:
                     keep_n.append(nz)
-                _lib.check(lib.smos_copy_paste_object(
-                    scan_ptrs[0], word_ptrs[0], first0, n5, slots, pts.data_ptr(), words.data_ptr(), ang.data_ptr(), flags.data_ptr(),
-                    status.data_ptr(), draws.count, i, bank.points.data_ptr() + int(bank.offsets[b]) * 16, m, at,
-                    bank.footprints.data_ptr() + b * 64, _lib.f64_array([vx * t * 0.1 for t in range(F)]),
-                    _lib.f64_array([vy * t * 0.1 for t in range(F)]), (ctypes.c_uint8 * preprocess.PASTE_TRIALS)(*draws.order[i].tolist()),
-                    self._cos, self._sin, None if nz is None else nz.data_ptr(), seed, sample_index,
-                    self.label_base + preprocess.paste_motion_label(draws.velocity[i]), work.data_ptr(), work.numel(),
-                    stream.cuda_stream), "smos_copy_paste_object")
+                _lib.call("smos_copy_paste_object", scan_ptrs[0], word_ptrs[0], first0, n5, slots, pts.data_ptr(), words.data_ptr(),
+                          ang.data_ptr(), flags.data_ptr(), status.data_ptr(), draws.count, i,
+                          bank.points.data_ptr() + int(bank.offsets[b]) * 16, m, at, bank.footprints.data_ptr() + b * 64,
+                          _lib.f64_array([vx * t * 0.1 for t in range(F)]), _lib.f64_array([vy * t * 0.1 for t in range(F)]),
+                          (ctypes.c_uint8 * preprocess.PASTE_TRIALS)(*draws.order[i].tolist()), self._cos, self._sin,
+                          None if nz is None else nz.data_ptr(), seed, sample_index,
+                          self.label_base + preprocess.paste_motion_label(draws.velocity[i]), work.data_ptr(), work.numel(),
+                          stream.cuda_stream)
             for t in keep_s + keep_w + keep_n:       # read by the launches above
                 t.record_stream(stream)
         out_scans, out_words, at = [], [], 0

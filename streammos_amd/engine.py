@@ -576,7 +576,7 @@ class InferenceEngine:
     def _encode_cl(self, point_feat, pcds_coord, pcds_sphere_coord, n_live=None):
         bs, t, cin, n, _ = point_feat.shape
         dev = point_feat.device
-        # views, not copies: the cross-view kernels take the strided slices as they lie (smos_gather_scatter_cl_view)
+        # views, not copies: the cross-view kernels take the strided slices as they lie (smos_gather_scatter_cl)
         bev_xy = pcds_coord[:, 0, :, :2, 0]
         sphere = pcds_sphere_coord[:, 0, :, :, 0]
         cpt = self.pp2[0].shape[0]

@@ -74,6 +74,20 @@ def _require_cuda(name, *tensors):
             raise RuntimeError("%s: expected a tensor in GPU memory, got device=%s (no CPU path here)" % (name, t.device))
 
 
+def _ptr(t):
+    """address of an optional tensor (None where it is absent)"""
+    return None if t is None else t.data_ptr()
+
+
+def _live_ptr(name, n_live):
+    """address of the optional ``n_live`` count of a wrapper: a device int32 tensor whose first element is read"""
+    if n_live is None:
+        return None
+    if n_live.dtype != torch.int32 or n_live.numel() < 1:
+        raise RuntimeError("%s: n_live must be a device int32 tensor" % name)
+    return n_live.data_ptr()
+
+
 def _flag(device):
     """4-byte "saw a negative feature" scratch of the scatter; one per (device, stream) so that launches on different
     HIP streams never share it."""
@@ -107,15 +121,11 @@ def voxel_maxpool_fwd(feat, ind, out, out_size, scale, voxel_max_idx=None):
         raise RuntimeError("voxel_maxpool_fwd: out has shape %s" % (tuple(out.shape),))
     if voxel_max_idx is not None and (voxel_max_idx.dtype != torch.int64 or not voxel_max_idx.is_contiguous()):
         raise RuntimeError("voxel_maxpool_fwd: voxel_max_idx must be contiguous int64")
-    lib = _lib.load()
     label = "voxel_maxpool_fwd[%dx%dx%d->%s]" % (bs, c, n, "x".join(str(int(s)) for s in out_size))
     with _on(feat.device), profiling.span(label):
-        rc = lib.smos_voxel_maxpool_fwd(
-            feat.data_ptr(), _lib.i64_array(feat.stride()[:3]), ind.data_ptr(), out.data_ptr(),
-            _lib.i64_array(out.stride()), voxel_max_idx.data_ptr() if voxel_max_idx is not None else None,
-            bs, c, n, d, _lib.i64_array(out_size), _lib.f32_array(scale), _dtype_code("voxel_maxpool_fwd", feat),
-            _flag(feat.device).data_ptr(), _stream(feat))
-    _lib.check(rc, "smos_voxel_maxpool_fwd")
+        _lib.call("smos_voxel_maxpool_fwd", feat.data_ptr(), _lib.i64_array(feat.stride()[:3]), ind.data_ptr(), out.data_ptr(),
+                  _lib.i64_array(out.stride()), _ptr(voxel_max_idx), bs, c, n, d, _lib.i64_array(out_size), _lib.f32_array(scale),
+                  _dtype_code("voxel_maxpool_fwd", feat), _flag(feat.device).data_ptr(), _stream(feat))
     return out
 
 
@@ -132,13 +142,10 @@ def voxel_maxpool_bwd(feat, ind, out, grad_out, grad_feat, out_size, scale):
     if not _same_layout(grad_feat, feat):
         raise RuntimeError("voxel_maxpool_bwd: grad_feat layout must match feat")
     bs, c, n = feat.shape[0], feat.shape[1], feat.shape[2]
-    lib = _lib.load()
     with _on(feat.device):
-        rc = lib.smos_voxel_maxpool_bwd(
-            feat.data_ptr(), _lib.i64_array(feat.stride()[:3]), ind.data_ptr(), out.data_ptr(), grad_out.data_ptr(),
-            _lib.i64_array(out.stride()), grad_feat.data_ptr(), bs, c, n, ind.shape[2], _lib.i64_array(out_size),
-            _lib.f32_array(scale), _dtype_code("voxel_maxpool_bwd", feat), _stream(feat))
-    _lib.check(rc, "smos_voxel_maxpool_bwd")
+        _lib.call("smos_voxel_maxpool_bwd", feat.data_ptr(), _lib.i64_array(feat.stride()[:3]), ind.data_ptr(), out.data_ptr(),
+                  grad_out.data_ptr(), _lib.i64_array(out.stride()), grad_feat.data_ptr(), bs, c, n, ind.shape[2],
+                  _lib.i64_array(out_size), _lib.f32_array(scale), _dtype_code("voxel_maxpool_bwd", feat), _stream(feat))
     return grad_feat
 
 
@@ -168,7 +175,7 @@ def is_deterministic():
 
 def segsum_chunk():
     """Terms per chunk of the fixed-order sums (tests place their edge cases around it)."""
-    return int(_lib.load().smos_segsum_chunk())
+    return _lib.query("smos_segsum_chunk")
 
 
 def _bilinear_gather_fwd(grid, coord, scale, out, point_major):
@@ -183,12 +190,9 @@ def _bilinear_gather_fwd(grid, coord, scale, out, point_major):
             out = torch.empty((b, n, c), dtype=torch.float32, device=grid.device).permute(0, 2, 1)
         else:
             out = torch.empty((b, c, n), dtype=torch.float32, device=grid.device)
-    lib = _lib.load()
     with _on(grid.device), profiling.span_f("bilinear_gather[%dx%dx%dx%d->%d]", (b, c, h, w, n)):
-        rc = lib.smos_bilinear_gather_fwd(grid.data_ptr(), _lib.i64_array(grid.stride()), coord.data_ptr(), k,
-                                          out.data_ptr(), _lib.i64_array(out.stride()[:3]), b, c, h, w, n,
-                                          _lib.f32_array(scale), _stream(grid))
-    _lib.check(rc, "smos_bilinear_gather_fwd")
+        _lib.call("smos_bilinear_gather_fwd", grid.data_ptr(), _lib.i64_array(grid.stride()), coord.data_ptr(), k, out.data_ptr(),
+                  _lib.i64_array(out.stride()[:3]), b, c, h, w, n, _lib.f32_array(scale), _stream(grid))
     return out
 
 
@@ -222,24 +226,20 @@ def bilinear_gather_backward(grad_out, coord, scale, grid_shape, channels_last=T
         grad_grid = torch.empty((b, h, w, c), dtype=torch.float32, device=grad_out.device).permute(0, 3, 1, 2)
     else:
         grad_grid = torch.empty((b, c, h, w), dtype=torch.float32, device=grad_out.device)
-    lib = _lib.load()
     if is_deterministic() if deterministic is None else deterministic:
-        need = int(lib.smos_bilinear_gather_bwd_det_work_bytes(b, c, h, w, n))
+        need = _lib.query("smos_bilinear_gather_bwd_det_work_bytes", b, c, h, w, n)
         if need < 0:
             raise RuntimeError("bilinear_gather_backward: the deterministic form takes B * N < 2^29 points and B * H * W < 2^31 - 1 "
                                "pixels (got %d, %d)" % (b * n, b * h * w))
         with _on(grad_out.device), profiling.span_f("bilinear_gather_bwd_det[%dx%dx%dx%d<-%d]", (b, c, h, w, n)):
             work = torch.empty((need,), dtype=torch.uint8, device=grad_out.device)     # on the current stream, like grad_grid
-            rc = lib.smos_bilinear_gather_bwd_det(grad_out.data_ptr(), _lib.i64_array(grad_out.stride()), coord.data_ptr(), k,
-                                                  grad_grid.data_ptr(), _lib.i64_array(grad_grid.stride()), b, c, h, w, n,
-                                                  _lib.f32_array(scale), work.data_ptr(), need, _stream(grad_out))
-        _lib.check(rc, "smos_bilinear_gather_bwd_det")
+            _lib.call("smos_bilinear_gather_bwd_det", grad_out.data_ptr(), _lib.i64_array(grad_out.stride()), coord.data_ptr(), k,
+                      grad_grid.data_ptr(), _lib.i64_array(grad_grid.stride()), b, c, h, w, n, _lib.f32_array(scale),
+                      work.data_ptr(), need, _stream(grad_out))
         return grad_grid
     with _on(grad_out.device), profiling.span_f("bilinear_gather_bwd[%dx%dx%dx%d<-%d]", (b, c, h, w, n)):
-        rc = lib.smos_bilinear_gather_bwd(grad_out.data_ptr(), _lib.i64_array(grad_out.stride()), coord.data_ptr(), k,
-                                          grad_grid.data_ptr(), _lib.i64_array(grad_grid.stride()), b, c, h, w, n,
-                                          _lib.f32_array(scale), _stream(grad_out))
-    _lib.check(rc, "smos_bilinear_gather_bwd")
+        _lib.call("smos_bilinear_gather_bwd", grad_out.data_ptr(), _lib.i64_array(grad_out.stride()), coord.data_ptr(), k,
+                  grad_grid.data_ptr(), _lib.i64_array(grad_grid.stride()), b, c, h, w, n, _lib.f32_array(scale), _stream(grad_out))
     return grad_grid
 
 
@@ -278,7 +278,7 @@ def bilinear_gather(grid, coord, scale, out=None, point_major=False):
 
 def seg_loss_tile():
     """Elements per block of the scan kernels of ``seg_loss`` (tests place their edge cases around it)."""
-    return int(_lib.load().smos_seg_loss_tile())
+    return _lib.query("smos_seg_loss_tile")
 
 
 def _seg_loss_args(name, pred, target):
@@ -313,8 +313,7 @@ class _SegLoss(torch.autograd.Function):
         p3 = pred[..., 0] if pred.dim() == 4 else pred
         b, c, p = p3.shape
         n = b * p
-        lib = _lib.load()
-        need = int(lib.smos_seg_loss_work_bytes(n, c))
+        need = _lib.query("smos_seg_loss_work_bytes", n, c)
         if need <= 0:
             raise RuntimeError("seg_loss: %d positions x %d classes is more than the sort is set up for" % (n, c))
         dev = pred.device
@@ -323,10 +322,9 @@ class _SegLoss(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=dev)
         stats = torch.empty(2, dtype=torch.float32, device=dev)
         with _on(dev), profiling.span_f("seg_loss[%dx%dx%d]", (b, c, p)):
-            rc = lib.smos_seg_loss_fwd(p3.data_ptr(), _lib.i64_array(p3.stride()), target.data_ptr(), b, c, p, k, top_weight,
-                                       lovasz_weight, ignore_index, coef.data_ptr(), loss.data_ptr(), stats.data_ptr(),
-                                       work.data_ptr(), need, _stream(pred))
-        _lib.check(rc, "smos_seg_loss_fwd")
+            _lib.call("smos_seg_loss_fwd", p3.data_ptr(), _lib.i64_array(p3.stride()), target.data_ptr(), b, c, p, k, top_weight,
+                      lovasz_weight, ignore_index, coef.data_ptr(), loss.data_ptr(), stats.data_ptr(), work.data_ptr(), need,
+                      _stream(pred))
         ctx.save_for_backward(pred, target, coef, stats)
         ctx.args = (k, float(top_weight), int(ignore_index), float(lovasz_weight))
         return loss
@@ -339,12 +337,10 @@ class _SegLoss(torch.autograd.Function):
         p3, g3 = (pred[..., 0], grad[..., 0]) if pred.dim() == 4 else (pred, grad)
         b, c, p = p3.shape
         go = grad_out.to(torch.float32).contiguous()
-        lib = _lib.load()
         with _on(pred.device), profiling.span_f("seg_loss_bwd[%dx%dx%d]", (b, c, p)):
-            rc = lib.smos_seg_loss_bwd(p3.data_ptr(), _lib.i64_array(p3.stride()), target.data_ptr(), coef.data_ptr(),
-                                       stats.data_ptr(), go.data_ptr(), b, c, p, k, top_weight, lovasz_weight, ignore_index,
-                                       g3.data_ptr(), _lib.i64_array(g3.stride()), _stream(pred))
-        _lib.check(rc, "smos_seg_loss_bwd")
+            _lib.call("smos_seg_loss_bwd", p3.data_ptr(), _lib.i64_array(p3.stride()), target.data_ptr(), coef.data_ptr(),
+                      stats.data_ptr(), go.data_ptr(), b, c, p, k, top_weight, lovasz_weight, ignore_index, g3.data_ptr(),
+                      _lib.i64_array(g3.stride()), _stream(pred))
         return grad, None, None, None, None, None
 
 
@@ -384,11 +380,11 @@ def point_mlp_fused():
 
 def point_mlp_chunk():
     """Points per chunk of partial sums of ``point_mlp_train`` (tests place their shapes around it)."""
-    return int(_lib.load().smos_point_mlp_chunk())
+    return _lib.query("smos_point_mlp_chunk")
 
 
 def _point_mlp_ptrs(tensors):
-    return (_lib.vp * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+    return (_lib.vp * len(tensors))(*[_ptr(t) for t in tensors])
 
 
 class _PointMlpTrain(torch.autograd.Function):
@@ -397,22 +393,20 @@ class _PointMlpTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, g0, b0, w1, g1, b1, w2, g2, b2, buffers, eps_mom, training):
-        lib = _lib.load()
         s, _, n = x.shape[:3]
         dev = x.device
-        need = int(lib.smos_point_mlp_work_bytes(s * n))
+        need = _lib.query("smos_point_mlp_work_bytes", s * n)
         if need <= 0:
             raise RuntimeError("point_mlp_train: %d x %d points is more than the kernels are set up for" % (s, n))
         work = _stream_workspace("point_mlp", (need,), torch.uint8, dev)
         y = torch.empty((s, 64, n, 1), dtype=torch.float32, device=dev)
-        fold = torch.empty(int(lib.smos_point_mlp_fold_floats()), dtype=torch.float32, device=dev)
-        dstat = torch.empty(int(lib.smos_point_mlp_stat_doubles()), dtype=torch.float64, device=dev)
+        fold = torch.empty(_lib.query("smos_point_mlp_fold_floats"), dtype=torch.float32, device=dev)
+        dstat = torch.empty(_lib.query("smos_point_mlp_stat_doubles"), dtype=torch.float64, device=dev)
         rm0, rv0, rm1, rv1, rm2, rv2 = buffers
         params = (g0, b0, rm0, rv0, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2)
         with _on(dev), profiling.span_f("point_mlp_%s[%dx%d]", ("train" if training else "eval", s, n)):
-            rc = lib.smos_point_mlp_fwd(x.data_ptr(), s, n, int(training), _point_mlp_ptrs(params), _lib.f64_array(eps_mom),
-                                        y.data_ptr(), fold.data_ptr(), dstat.data_ptr(), work.data_ptr(), need, _stream(x))
-        _lib.check(rc, "smos_point_mlp_fwd")
+            _lib.call("smos_point_mlp_fwd", x.data_ptr(), s, n, int(training), _point_mlp_ptrs(params), _lib.f64_array(eps_mom),
+                      y.data_ptr(), fold.data_ptr(), dstat.data_ptr(), work.data_ptr(), need, _stream(x))
         ctx.save_for_backward(x, g0, b0, w1, g1, b1, w2, g2, b2, fold, dstat)
         ctx.buffers, ctx.eps_mom, ctx.training = buffers, eps_mom, bool(training)
         return y
@@ -421,7 +415,6 @@ class _PointMlpTrain(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_y):
         x, g0, b0, w1, g1, b1, w2, g2, b2, fold, dstat = ctx.saved_tensors
-        lib = _lib.load()
         s, _, n = x.shape[:3]
         dev = x.device
         gy = grad_y.to(torch.float32).contiguous()
@@ -429,13 +422,12 @@ class _PointMlpTrain(torch.autograd.Function):
         params = (g0, b0, rm0, rv0, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2)
         grads = [torch.empty_like(p) if ctx.needs_input_grad[1 + i] else None for i, p in enumerate((g0, b0, w1, g1, b1, w2, g2, b2))]
         if any(g is not None for g in grads):
-            need = int(lib.smos_point_mlp_work_bytes(s * n))
+            need = _lib.query("smos_point_mlp_work_bytes", s * n)
             work = _stream_workspace("point_mlp", (need,), torch.uint8, dev)
             with _on(dev), profiling.span_f("point_mlp_bwd[%dx%d]", (s, n)):
-                rc = lib.smos_point_mlp_bwd(x.data_ptr(), gy.data_ptr(), s, n, int(ctx.training), _point_mlp_ptrs(params),
-                                            _lib.f64_array(ctx.eps_mom), fold.data_ptr(), dstat.data_ptr(), _point_mlp_ptrs(grads),
-                                            work.data_ptr(), need, _stream(x))
-            _lib.check(rc, "smos_point_mlp_bwd")
+                _lib.call("smos_point_mlp_bwd", x.data_ptr(), gy.data_ptr(), s, n, int(ctx.training), _point_mlp_ptrs(params),
+                          _lib.f64_array(ctx.eps_mom), fold.data_ptr(), dstat.data_ptr(), _point_mlp_ptrs(grads), work.data_ptr(),
+                          need, _stream(x))
         return (None, *grads, None, None, None)
 
 
@@ -501,12 +493,10 @@ def msda_fwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight
     n, s, m, d = value.shape
     lq, l, p = sampling_loc.shape[1], sampling_loc.shape[3], sampling_loc.shape[4]
     out = torch.empty((n, lq, m * d), dtype=value.dtype, device=value.device)
-    lib = _lib.load()
     with _on(value.device), profiling.span_f("msda_fwd[%dx%dx%dx%d]", (n, lq, m, d)):
-        rc = lib.smos_msda_fwd(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                               sampling_loc.data_ptr(), attn_weight.data_ptr(), out.data_ptr(), n, s, m, d, l, lq, p,
-                               _dtype_code("ms_deform_attn_forward", value), _stream(value))
-    _lib.check(rc, "smos_msda_fwd")
+        _lib.call("smos_msda_fwd", value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                  sampling_loc.data_ptr(), attn_weight.data_ptr(), out.data_ptr(), n, s, m, d, l, lq, p,
+                  _dtype_code("ms_deform_attn_forward", value), _stream(value))
     return out
 
 
@@ -531,29 +521,25 @@ def msda_bwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight
     g_value = torch.empty_like(value) if det else torch.zeros_like(value)      # the fixed-order form writes every element
     g_loc = torch.empty_like(sampling_loc)
     g_attn = torch.empty_like(attn_weight)
-    lib = _lib.load()
     if det:
         for name, t in (("sampling_loc", sampling_loc), ("attn_weight", attn_weight), ("grad_output", grad_output)):
             if t.dtype != torch.float32:
                 raise RuntimeError("ms_deform_attn_backward: %s is %s, value float32" % (name, t.dtype))
-        need = int(lib.smos_msda_bwd_det_work_bytes(n, s, m, d, l, lq, p))
+        need = _lib.query("smos_msda_bwd_det_work_bytes", n, s, m, d, l, lq, p)
         if need < 0:
             raise RuntimeError("ms_deform_attn_backward: the deterministic form takes fewer than 2^29 samples and 2^31 - 1 value "
                                "rows (got %d, %d)" % (n * lq * m * l * p, n * s * m))
         with _on(value.device), profiling.span_f("msda_bwd_det[%dx%dx%dx%d]", (n, lq, m, d)):
             work = torch.empty((need,), dtype=torch.uint8, device=value.device)
-            rc = lib.smos_msda_bwd_det(grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(),
-                                       level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
-                                       g_value.data_ptr(), g_loc.data_ptr(), g_attn.data_ptr(), n, s, m, d, l, lq, p,
-                                       work.data_ptr(), need, _stream(value))
-        _lib.check(rc, "smos_msda_bwd_det")
+            _lib.call("smos_msda_bwd_det", grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(),
+                      level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(), g_value.data_ptr(),
+                      g_loc.data_ptr(), g_attn.data_ptr(), n, s, m, d, l, lq, p, work.data_ptr(), need, _stream(value))
         return g_value, g_loc, g_attn
     with _on(value.device), profiling.span_f("msda_bwd[%dx%dx%dx%d]", (n, lq, m, d)):
-        rc = lib.smos_msda_bwd(grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                               sampling_loc.data_ptr(), attn_weight.data_ptr(), g_value.data_ptr(), g_loc.data_ptr(),
-                               g_attn.data_ptr(), n, s, m, d, l, lq, p, _dtype_code("ms_deform_attn_backward", value),
-                               _stream(value))
-    _lib.check(rc, "smos_msda_bwd")
+        _lib.call("smos_msda_bwd", grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(),
+                  level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(), g_value.data_ptr(),
+                  g_loc.data_ptr(), g_attn.data_ptr(), n, s, m, d, l, lq, p, _dtype_code("ms_deform_attn_backward", value),
+                  _stream(value))
     return g_value, g_loc, g_attn
 
 
@@ -566,20 +552,15 @@ def tta_argmax(pred, want_prob=False):
     b, k, n = pred.shape
     labels = torch.empty(n, dtype=torch.uint8, device=pred.device)
     prob = torch.empty((n, k), dtype=torch.float32, device=pred.device) if want_prob else None
-    lib = _lib.load()
     with _on(pred.device):
-        rc = lib.smos_tta_argmax(pred.data_ptr(), b, k, n, labels.data_ptr(), prob.data_ptr() if want_prob else None,
-                                 _stream(pred))
-    _lib.check(rc, "smos_tta_argmax")
+        _lib.call("smos_tta_argmax", pred.data_ptr(), b, k, n, labels.data_ptr(), _ptr(prob), _stream(pred))
     return (labels, prob) if want_prob else labels
 
 
 def vote_clear(table):
     _require_cuda("vote_clear", table)
-    lib = _lib.load()
     with _on(table.device):
-        rc = lib.smos_vote_clear(table.data_ptr(), _stream(table))
-    _lib.check(rc, "smos_vote_clear")
+        _lib.call("smos_vote_clear", table.data_ptr(), _stream(table))
 
 
 def vote_accumulate(points, labels, table, pose_diff=None, recip_quantize=False):
@@ -590,11 +571,9 @@ def vote_accumulate(points, labels, table, pose_diff=None, recip_quantize=False)
     pose = None
     if pose_diff is not None:
         pose = _lib.f64_array([float(v) for v in pose_diff.reshape(-1)[:16]])
-    lib = _lib.load()
     with _on(points.device):
-        rc = lib.smos_vote_accumulate(points.data_ptr(), points.shape[0], points.stride(0), labels.data_ptr(), pose,
-                                      1 if recip_quantize else 0, table.data_ptr(), _stream(points))
-    _lib.check(rc, "smos_vote_accumulate")
+        _lib.call("smos_vote_accumulate", points.data_ptr(), points.shape[0], points.stride(0), labels.data_ptr(), pose,
+                  1 if recip_quantize else 0, table.data_ptr(), _stream(points))
 
 
 def vote_accumulate_frames(frames, table, recip_quantize=False):
@@ -620,22 +599,17 @@ def vote_accumulate_frames(frames, table, recip_quantize=False):
                 raise RuntimeError("vote_accumulate_frames: pose_diff must be 4x4")
             keep.append(arr)                          # the numpy buffer is read during the call
             pose[f] = arr.ctypes.data_as(_lib.c_f64p)
-    lib = _lib.load()
     with _on(table.device), profiling.span_f("vote_accumulate[%dx%d]", (count, max(n))):
-        rc = lib.smos_vote_accumulate_frames(count, pts, n, stride, lab, pose, 1 if recip_quantize else 0, table.data_ptr(),
-                                             _stream(table))
-    _lib.check(rc, "smos_vote_accumulate_frames")
+        _lib.call("smos_vote_accumulate_frames", count, pts, n, stride, lab, pose, 1 if recip_quantize else 0, table.data_ptr(),
+                  _stream(table))
 
 
 def vote_resolve(points, labels, table, lut=None, recip_quantize=False):
     _require_cuda("vote_resolve", points, labels, table, lut)
     out = torch.empty(points.shape[0], dtype=torch.int32, device=points.device)
-    lib = _lib.load()
     with _on(points.device):
-        rc = lib.smos_vote_resolve(points.data_ptr(), points.shape[0], points.stride(0), labels.data_ptr(),
-                                   1 if recip_quantize else 0, table.data_ptr(),
-                                   lut.data_ptr() if lut is not None else None, out.data_ptr(), _stream(points))
-    _lib.check(rc, "smos_vote_resolve")
+        _lib.call("smos_vote_resolve", points.data_ptr(), points.shape[0], points.stride(0), labels.data_ptr(),
+                  1 if recip_quantize else 0, table.data_ptr(), _ptr(lut), out.data_ptr(), _stream(points))
     return out
 
 
@@ -650,16 +624,14 @@ def dbscan(points, eps, min_samples, max_sweeps=4096):
     labels = torch.empty(n, dtype=torch.int32, device=points.device)
     if n == 0:
         return labels
-    lib = _lib.load()
-    need = int(lib.smos_dbscan_work_bytes(n))
+    need = _lib.query("smos_dbscan_work_bytes", n)
     if need <= 0:
         raise RuntimeError("dbscan: workspace query failed for n=%d" % n)
     work = torch.empty(need + 256, dtype=torch.uint8, device=points.device)
     base = (work.data_ptr() + 255) // 256 * 256
     with _on(points.device):
-        rc = lib.smos_dbscan(points.data_ptr(), n, points.stride(0), float(eps), int(min_samples), labels.data_ptr(),
-                             base, need, int(max_sweeps), _stream(points))
-    _lib.check(rc, "smos_dbscan")
+        _lib.call("smos_dbscan", points.data_ptr(), n, points.stride(0), float(eps), int(min_samples), labels.data_ptr(), base,
+                  need, int(max_sweeps), _stream(points))
     return labels
 
 
@@ -676,11 +648,9 @@ def box_vote(points, labels, boxes, counts, pose_diff=None):
     pose = None
     if pose_diff is not None:
         pose = _lib.f64_array([float(v) for v in pose_diff.reshape(-1)[:16]])
-    lib = _lib.load()
     with _on(points.device):
-        rc = lib.smos_box_vote(points.data_ptr(), points.shape[0], points.stride(0), labels.data_ptr(), pose,
-                               boxes.data_ptr(), boxes.shape[0], counts.data_ptr(), _stream(points))
-    _lib.check(rc, "smos_box_vote")
+        _lib.call("smos_box_vote", points.data_ptr(), points.shape[0], points.stride(0), labels.data_ptr(), pose, boxes.data_ptr(),
+                  boxes.shape[0], counts.data_ptr(), _stream(points))
     return counts
 
 
@@ -689,7 +659,7 @@ MAX_BOXES = 2048        # upper bound of max_boxes (the LDS of the box vote)
 
 def instance_work_bytes(n):
     """Device scratch smos_instance_cluster needs for a scan of n points (256 bytes of slack for the alignment included)."""
-    need = int(_lib.load().smos_instance_work_bytes(int(n)))
+    need = _lib.query("smos_instance_work_bytes", int(n))
     if need < 0:
         raise RuntimeError("instance_cluster: workspace query failed for n=%d" % n)
     return need + 256
@@ -722,7 +692,6 @@ def instance_cluster(points, bf, eps, min_samples, min_points, floor_lift, max_b
         if t.dtype != dtype or t.numel() != numel or not t.is_contiguous() or t.device != dev:
             raise RuntimeError("instance_cluster: out[%r] must be a contiguous %s tensor of %d elements on the points' device"
                                % (key, dtype, numel))
-    lib = _lib.load()
     need = instance_work_bytes(n)
     if work is None:
         work = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -731,11 +700,9 @@ def instance_cluster(points, bf, eps, min_samples, min_points, floor_lift, max_b
     if work.dtype != torch.uint8 or not work.is_contiguous() or work.device != dev or room < need - 256:
         raise RuntimeError("instance_cluster: work must be a contiguous uint8 tensor of >= %d bytes on the points' device" % need)
     with _on(dev), profiling.span_f("instance_cluster[%d]", (n,)):
-        rc = lib.smos_instance_cluster(points.data_ptr(), n, points.stride(0), bf.data_ptr(), float(eps), int(min_samples),
-                                       int(min_points), float(floor_lift), max_boxes, out["names"].data_ptr(),
-                                       out["boxes"].data_ptr(), out["slot_of"].data_ptr(), out["k"].data_ptr(),
-                                       out["status"].data_ptr(), base, room, _stream(points))
-    _lib.check(rc, "smos_instance_cluster")
+        _lib.call("smos_instance_cluster", points.data_ptr(), n, points.stride(0), bf.data_ptr(), float(eps), int(min_samples),
+                  int(min_points), float(floor_lift), max_boxes, out["names"].data_ptr(), out["boxes"].data_ptr(),
+                  out["slot_of"].data_ptr(), out["k"].data_ptr(), out["status"].data_ptr(), base, room, _stream(points))
     return out
 
 
@@ -771,11 +738,9 @@ def box_vote_dev(frames, boxes, k, counts):
                 raise RuntimeError("box_vote_dev: pose_diff must be 4x4")
             keep.append(arr)                          # the numpy buffer is read during the call
             pose[f] = arr.ctypes.data_as(_lib.c_f64p)
-    lib = _lib.load()
     with _on(boxes.device), profiling.span_f("box_vote_dev[%dx%d]", (count, max(n))):
-        rc = lib.smos_box_vote_dev(count, pts, n, stride, lab, pose, boxes.data_ptr(), k.data_ptr(), boxes.shape[0],
-                                   counts.data_ptr(), _stream(boxes))
-    _lib.check(rc, "smos_box_vote_dev")
+        _lib.call("smos_box_vote_dev", count, pts, n, stride, lab, pose, boxes.data_ptr(), k.data_ptr(), boxes.shape[0],
+                  counts.data_ptr(), _stream(boxes))
     return counts
 
 
@@ -792,11 +757,9 @@ def instance_apply(names, slot_of, counts, k, labels):
         raise RuntimeError("instance_apply: counts must be a contiguous 32-bit [max_boxes, 3] tensor on the labels' device")
     if k.dtype != torch.int32 or k.numel() != 1 or k.device != labels.device:
         raise RuntimeError("instance_apply: k must be an int32 [1] tensor on the labels' device")
-    lib = _lib.load()
     with _on(labels.device):
-        rc = lib.smos_instance_apply(names.data_ptr(), slot_of.data_ptr(), counts.data_ptr(), k.data_ptr(), counts.shape[0],
-                                     labels.data_ptr(), n, _stream(labels))
-    _lib.check(rc, "smos_instance_apply")
+        _lib.call("smos_instance_apply", names.data_ptr(), slot_of.data_ptr(), counts.data_ptr(), k.data_ptr(), counts.shape[0],
+                  labels.data_ptr(), n, _stream(labels))
     return labels
 
 
@@ -807,7 +770,7 @@ def _label_args(name, words, gt, gt_map, counts, n, device):
                               or words.data_ptr() % 16 or words.device != device):
         raise RuntimeError("%s: words must be a contiguous, 16-byte aligned int32 tensor of >= n elements on the labels' device" % name)
     if gt is None:
-        return (words.data_ptr() if words is not None else None), None, None, 0, None
+        return _ptr(words), None, None, 0, None
     if gt_map is None or counts is None:
         raise RuntimeError("%s: counting needs gt_map and counts" % name)
     if gt.dtype not in (torch.int32, torch.uint32) or not gt.is_contiguous() or gt.numel() != n or gt.data_ptr() % 16:
@@ -818,7 +781,7 @@ def _label_args(name, words, gt, gt_map, counts, n, device):
         raise RuntimeError("%s: counts must be a contiguous 64-bit tensor of 6 counters" % name)
     if not (gt.device == gt_map.device == counts.device == device):
         raise RuntimeError("%s: every tensor must be on the labels' device" % name)
-    return (words.data_ptr() if words is not None else None), gt.data_ptr(), gt_map.data_ptr(), gt_map.numel(), counts.data_ptr()
+    return _ptr(words), gt.data_ptr(), gt_map.data_ptr(), gt_map.numel(), counts.data_ptr()
 
 
 def label_words(labels, words=None, lut=True, gt=None, gt_map=None, counts=None):
@@ -834,10 +797,8 @@ def label_words(labels, words=None, lut=True, gt=None, gt_map=None, counts=None)
     if words is None:
         words = torch.empty(n, dtype=torch.int32, device=labels.device)
     w, g, gm, mn, c = _label_args("label_words", words, gt, gt_map, counts, n, labels.device)
-    lib = _lib.load()
     with _on(labels.device):
-        rc = lib.smos_label_words(labels.data_ptr(), n, 1 if lut else 0, w, g, gm, mn, c, _stream(labels))
-    _lib.check(rc, "smos_label_words")
+        _lib.call("smos_label_words", labels.data_ptr(), n, 1 if lut else 0, w, g, gm, mn, c, _stream(labels))
     return words
 
 
@@ -849,10 +810,8 @@ def voted_label_counts(voted, gt, gt_map, counts, words=None):
         raise RuntimeError("voted_label_counts: voted must be a contiguous, 16-byte aligned int32 vector")
     n = voted.shape[0]
     w, g, gm, mn, c = _label_args("voted_label_counts", words, gt, gt_map, counts, n, voted.device)
-    lib = _lib.load()
     with _on(voted.device):
-        rc = lib.smos_label_count_voted(voted.data_ptr(), n, w, g, gm, mn, c, _stream(voted))
-    _lib.check(rc, "smos_label_count_voted")
+        _lib.call("smos_label_count_voted", voted.data_ptr(), n, w, g, gm, mn, c, _stream(voted))
     return words
 
 
@@ -887,21 +846,18 @@ def pointnet_scatter(xyzi, coord, w1, b1, w2, b2, bev, pts_out=None, zero_fill=F
     po_b = po_n = 0
     if pts_out is not None:
         po_b, po_n = _rows("pointnet_scatter", pts_out, cout)
-    lib = _lib.load()
     with _on(xyzi.device), profiling.span_f("pointnet_scatter[%dx%dx%d->%dx%d]", (b, t, n, h, w)):
         if zero_fill:
             bev.zero_()
-        rc = lib.smos_pointnet_scatter(xyzi.data_ptr(), coord.data_ptr(), k, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                       b2.data_ptr(), bev.data_ptr(), pts_out.data_ptr() if pts_out is not None else None,
-                                       po_b, po_n, b, t, n, h, w, cin, w1.shape[0], cout, _stream(xyzi))
-    _lib.check(rc, "smos_pointnet_scatter")
+        _lib.call("smos_pointnet_scatter", xyzi.data_ptr(), coord.data_ptr(), k, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                  b2.data_ptr(), bev.data_ptr(), _ptr(pts_out), po_b, po_n, b, t, n, h, w, cin, w1.shape[0], cout, _stream(xyzi))
     return bev
 
 
 def point_head_k_order():
     """[96, 2] int64: the input channel k-step s of layer 1 feeds to lane half h.  A row is three 64-channel segments (point
     MLP | BEV | range view); steps [32 t, 32 t + 32) walk segment t, lane half h its channels [32 h, 32 h + 32) -- the same walk
-    for both halves, so that one segment (the BEV one, smos_point_head_gather_live) can come from somewhere else than the row."""
+    for both halves, so that one segment (the BEV one, smos_point_head_gather) can come from somewhere else than the row."""
     s = torch.arange(96)[:, None]
     h = torch.arange(2)[None, :]
     return 64 * (s >> 5) + 32 * h + (s & 31)
@@ -930,7 +886,7 @@ def point_head_prepare(l1, l2, l3):
     b3p = torch.zeros(32, device=dev)
     b3p[:b3.shape[0]] = b3
     flat = torch.cat([a1.reshape(-1), a2.reshape(-1), a3.reshape(-1), b1, b2, b3p]).contiguous()
-    if flat.numel() != int(_lib.load().smos_point_head_weight_floats()):
+    if flat.numel() != _lib.query("smos_point_head_weight_floats"):
         raise RuntimeError("point_head_prepare: weight block has %d floats" % flat.numel())
     return flat, int(w3.shape[0])
 
@@ -946,8 +902,7 @@ def point_head(rows, wprep, m3, out=None, n_live=None, gather=None):
     _require_cuda("point_head", rows, wprep, out, n_live)
     if rows.dtype != torch.float32 or rows.dim() != 3 or rows.stride(2) != 1 or rows.stride(0) != rows.shape[1] * rows.stride(1):
         raise RuntimeError("point_head: rows must be a float32 [B, N, C] tensor with dense point rows")
-    if n_live is not None and (n_live.dtype != torch.int32 or n_live.numel() < 1):
-        raise RuntimeError("point_head: n_live must be a device int32 tensor")
+    live = _live_ptr("point_head", n_live)
     b, n = rows.shape[0], rows.shape[1]
     if gather is not None:
         grid, gcoord, gscale = gather
@@ -958,17 +913,13 @@ def point_head(rows, wprep, m3, out=None, n_live=None, gather=None):
         kg, gbs = _coord_view("point_head", gcoord, b, n)
     if out is None:
         out = torch.empty((b, m3, n), dtype=torch.float32, device=rows.device)
-    lib = _lib.load()
-    live = n_live.data_ptr() if n_live is not None else None
+    head = (rows.data_ptr(), rows.stride(1), wprep.data_ptr(), out.data_ptr(), b, n, 192, 96, 64, m3, live)
     with _on(rows.device), profiling.span_f("point_head[%dx%d]", (b, n)):
         if gather is None:
-            rc = lib.smos_point_head_live(rows.data_ptr(), rows.stride(1), wprep.data_ptr(), out.data_ptr(), b, n, 192, 96, 64, m3,
-                                          live, _stream(rows))
+            _lib.call("smos_point_head", *head, _stream(rows))
         else:
-            rc = lib.smos_point_head_gather_live(rows.data_ptr(), rows.stride(1), wprep.data_ptr(), out.data_ptr(), b, n, 192, 96, 64,
-                                                 m3, live, grid.data_ptr(), gp, grid.shape[2], grid.shape[3], gcoord.data_ptr(), kg,
-                                                 gbs, _lib.f32_array(gscale), _stream(rows))
-    _lib.check(rc, "smos_point_head_live" if gather is None else "smos_point_head_gather_live")
+            _lib.call("smos_point_head_gather", *head, grid.data_ptr(), gp, grid.shape[2], grid.shape[3], gcoord.data_ptr(), kg, gbs,
+                      _lib.f32_array(gscale), _stream(rows))
     return out
 
 
@@ -1035,8 +986,8 @@ def _conv_operands(name, x, wprep, bias, cout, ho, wo, residual=None, out=None, 
                                   tuple(chan_sums.shape) != (b, sum_chunks(ho, wo), cout)):
         raise RuntimeError("%s: chan_sums must be contiguous float32 [B, %s(Ho, Wo), Cout], without a residual"
                            % (name, sum_chunks.__name__))
-    return out, (x.data_ptr(), _cl(name, x), wprep.data_ptr(), bias.data_ptr() if bias is not None else None,
-                 residual.data_ptr() if residual is not None else None, _cl(name, residual) if residual is not None else 0,
+    return out, (x.data_ptr(), _cl(name, x), wprep.data_ptr(), _ptr(bias), _ptr(residual),
+                 _cl(name, residual) if residual is not None else 0,
                  out.data_ptr(), _cl(name, out))
 
 
@@ -1049,9 +1000,9 @@ def _conv_launch(fn_name, family, args, keep, x, label_fn):
     """One conv launch of the C function `fn_name` on x's device and torch's current stream.  While nothing is profiled that is
     all (no label, no span: a label is a string format of ~10 numbers); otherwise the launch carries label_fn() under the
     kernel family, and a requested replay gets a closure over args (`keep`: the operand tensors, alive as long as it is)."""
-    fn = getattr(_lib.load(), fn_name)
     dev = x.device
     if not profiling.enabled():
+        fn = _lib.entry(fn_name)             # not _lib.call: its frame and second argument tuple show in the per-launch cost
         with _on(dev):
             rc = fn(*args, _raw_stream(_dev_index(dev)))
         if rc:
@@ -1059,12 +1010,11 @@ def _conv_launch(fn_name, family, args, keep, x, label_fn):
         return
     label = label_fn()
     with _on(dev), profiling.span(label, family):
-        rc = fn(*args, _stream(x))
-    _lib.check(rc, fn_name)
+        _lib.call(fn_name, *args, _stream(x))
     if profiling._replay_label == label:
         def again(keep=keep):
             with _on(keep[0].device), profiling.span(label, family):
-                _lib.check(fn(*args, _stream(keep[0])), fn_name)
+                _lib.call(fn_name, *args, _stream(keep[0]))
         profiling.offer_replay(label, again)
 
 
@@ -1077,7 +1027,7 @@ def conv_rows_cl(x, wprep, bias, act, cout, kernel, mt=1, residual=None, out=Non
     if not conv_rows_ok(kernel, 1, cin, cout) or wprep.numel() != cout * cin * kh * kw or mt not in (1, 2) or cout % (32 * mt):
         raise RuntimeError("conv_rows_cl: unsupported shape %s k%dx%d -> %d" % (tuple(x.shape), kh, kw, cout))
     out, head = _conv_operands("conv_rows_cl", x, wprep, bias, cout, h, w, residual, out, chan_sums, conv_sum_chunks)
-    args = head + (b, h, w, cin, cout, kh, kw, int(mt), int(act), chan_sums.data_ptr() if chan_sums is not None else None)
+    args = head + (b, h, w, cin, cout, kh, kw, int(mt), int(act), _ptr(chan_sums))
     _conv_launch("smos_conv_rows_cl", "conv_rows", args, (x, wprep, bias, residual, out, chan_sums), x,
                  lambda: _conv_label("conv_cl", x, cout, h, w, kernel, residual))
     return out
@@ -1114,8 +1064,7 @@ def conv_cl(x, wprep, bias, act, cout, kernel, stride=1, padding=None, mt=1, res
     if wprep.numel() != cout * cin * kh * kw:
         raise RuntimeError("conv_cl: weight block has %d floats, expected %d" % (wprep.numel(), cout * cin * kh * kw))
     out, head = _conv_operands("conv_cl", x, wprep, bias, cout, ho, wo, residual, out, chan_sums, conv_sum_chunks)
-    args = head + (b, h, w, cin, cout, kh, kw, stride, ph, pw, mt, int(act),
-                   chan_sums.data_ptr() if chan_sums is not None else None)
+    args = head + (b, h, w, cin, cout, kh, kw, stride, ph, pw, mt, int(act), _ptr(chan_sums))
     _conv_launch("smos_conv_cl", "conv_igemm", args, (x, wprep, bias, residual, out, chan_sums), x,
                  lambda: _conv_label("conv_cl", x, cout, ho, wo, kernel, residual))
     return out
@@ -1150,7 +1099,7 @@ def conv_bf16_ok(x, cout, kernel, stride=1, residual=None, out=None, chan_sums=N
     key = (x.shape[1], cout, kh, kw, stride, residual is not None)
     ok = _bf16_shape_ok.get(key)
     if ok is None:
-        ok = _bf16_shape_ok[key] = bool(_lib.load().smos_conv_bf16_cl_supported(*key[:5], int(key[5])))
+        ok = _bf16_shape_ok[key] = bool(_lib.query("smos_conv_bf16_cl_supported", *key[:5], int(key[5])))
     return ok
 
 
@@ -1171,7 +1120,7 @@ def conv_bf16_cl(x, wprep, bias, act, cout, kernel, stride=1, padding=None, resi
     if (out is not None and out.dtype != torch.float32) or (residual is not None and residual.dtype != torch.float32):
         raise RuntimeError("conv_bf16_cl: out and residual must be float32")
     out, head = _conv_operands("conv_bf16_cl", x, wprep, bias, cout, ho, wo, residual, out, chan_sums, conv_sum_chunks)
-    args = head + (b, h, w, cin, cout, kh, kw, stride, ph, pw, int(act), chan_sums.data_ptr() if chan_sums is not None else None)
+    args = head + (b, h, w, cin, cout, kh, kw, stride, ph, pw, int(act), _ptr(chan_sums))
     _conv_launch("smos_conv_bf16_cl", "conv_bf16", args, (x, wprep, bias, residual, out, chan_sums), x,
                  lambda: _conv_label("conv_bf16", x, cout, ho, wo, kernel, residual))
     return out
@@ -1220,7 +1169,7 @@ def conv_wino_cl(x, wprep, bias, act, cout, mb=2, residual=None, out=None, chan_
     if not conv_wino_ok((3, 3), 1, cin, cout) or mb not in (1, 2) or cout % (16 * mb) or wprep.numel() != 16 * cout * cin:
         raise RuntimeError("conv_wino_cl: unsupported shape %s -> %d (mb=%d)" % (tuple(x.shape), cout, mb))
     out, head = _conv_operands("conv_wino_cl", x, wprep, bias, cout, h, w, residual, out, chan_sums, conv_wino_sum_chunks)
-    args = head + (b, h, w, cin, cout, int(mb), int(act), chan_sums.data_ptr() if chan_sums is not None else None)
+    args = head + (b, h, w, cin, cout, int(mb), int(act), _ptr(chan_sums))
     _conv_launch("smos_conv_wino_cl", "conv_wino", args, (x, wprep, bias, residual, out, chan_sums), x,
                  lambda: _conv_label("conv_cl", x, cout, h, w, (3, 3), residual))
     return out
@@ -1286,11 +1235,9 @@ def unbalance_block_cl(x, plan, both=None, out=None):
     if both.shape != (b, 2 * c, h, w) or out.shape != x.shape:
         raise RuntimeError("unbalance_block_cl: both must be [B,2C,H,W] and out have x's shape %s" % (tuple(x.shape),))
     with _on(dev):
-        rc = _lib.load().smos_unbalance_block_cl(x.data_ptr(), _cl("unbalance_block_cl", x), *plan.ptrs_a, *plan.ptrs_b, *plan.ptrs_c,
-                                                 both.data_ptr(), _cl("unbalance_block_cl", both), out.data_ptr(),
-                                                 _cl("unbalance_block_cl", out), b, h, w, c, plan.mb, _raw_stream(_dev_index(dev)))
-    if rc:
-        _lib.check(rc, "smos_unbalance_block_cl")
+        _lib.call("smos_unbalance_block_cl", x.data_ptr(), _cl("unbalance_block_cl", x), *plan.ptrs_a, *plan.ptrs_b, *plan.ptrs_c,
+                  both.data_ptr(), _cl("unbalance_block_cl", both), out.data_ptr(), _cl("unbalance_block_cl", out), b, h, w, c,
+                  plan.mb, _raw_stream(_dev_index(dev)))
     return out
 
 
@@ -1319,18 +1266,15 @@ def basic_block_cl(x, plan, y=None, out=None, ws=None):
         out = empty_cl(b, c, h, w, dev)
     if y.shape != x.shape or out.shape != x.shape:
         raise RuntimeError("basic_block_cl: y / out must have x's shape %s" % (tuple(x.shape),))
-    lib = _lib.load()
     wsp = None
     if plan.gated:
-        if ws is None or ws.dtype != torch.float32 or not ws.is_contiguous() or ws.numel() < lib.smos_basic_block_ws_floats(b, h, w, c):
+        if (ws is None or ws.dtype != torch.float32 or not ws.is_contiguous() or
+                ws.numel() < _lib.query("smos_basic_block_ws_floats", b, h, w, c)):
             raise RuntimeError("basic_block_cl: a gated block needs smos_basic_block_ws_floats floats of contiguous scratch")
         wsp = ws.data_ptr()
     with _on(dev):
-        rc = lib.smos_basic_block_cl(x.data_ptr(), _cl("basic_block_cl", x), *plan.ptrs, y.data_ptr(), _cl("basic_block_cl", y),
-                                     out.data_ptr(), _cl("basic_block_cl", out), wsp, b, h, w, c, plan.mb,
-                                     _raw_stream(_dev_index(dev)))
-    if rc:
-        _lib.check(rc, "smos_basic_block_cl")
+        _lib.call("smos_basic_block_cl", x.data_ptr(), _cl("basic_block_cl", x), *plan.ptrs, y.data_ptr(), _cl("basic_block_cl", y),
+                  out.data_ptr(), _cl("basic_block_cl", out), wsp, b, h, w, c, plan.mb, _raw_stream(_dev_index(dev)))
     return out
 
 
@@ -1341,10 +1285,8 @@ def msda_fwd_qp(value, qp, h, w, points):
     if not (value.is_contiguous() and qp.is_contiguous()) or s != h * w or qp.shape[-1] != m * points * 3 or value.dtype != torch.float32:
         raise RuntimeError("msda_fwd_qp: expected contiguous float32 value [N,H*W,M,D] and qp [N,H*W,M*P*3]")
     out = torch.empty((n, s, m * d), dtype=torch.float32, device=value.device)
-    lib = _lib.load()
     with _on(value.device), profiling.span_f("msda_fwd[%dx%dx%dx%d]", (n, s, m, d)):
-        rc = lib.smos_msda_fwd_qp(value.data_ptr(), qp.data_ptr(), out.data_ptr(), n, h, w, m, d, points, _stream(value))
-    _lib.check(rc, "smos_msda_fwd_qp")
+        _lib.call("smos_msda_fwd_qp", value.data_ptr(), qp.data_ptr(), out.data_ptr(), n, h, w, m, d, points, _stream(value))
     return out
 
 
@@ -1355,11 +1297,9 @@ def add_layer_norm(x, res, gamma, beta, eps=1e-5):
         raise RuntimeError("add_layer_norm: x and res must be contiguous and of equal shape")
     c = x.shape[-1]
     out = torch.empty_like(x)
-    lib = _lib.load()
     with _on(x.device):
-        rc = lib.smos_add_layer_norm(x.data_ptr(), res.data_ptr() if res is not None else None, gamma.data_ptr(), beta.data_ptr(),
-                                     out.data_ptr(), x.numel() // c, c, float(eps), _stream(x))
-    _lib.check(rc, "smos_add_layer_norm")
+        _lib.call("smos_add_layer_norm", x.data_ptr(), _ptr(res), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(), x.numel() // c,
+                  c, float(eps), _stream(x))
     return out
 
 
@@ -1424,9 +1364,8 @@ class TfusionLayer:
         self.ffn = int(ffn)
         self.eps1 = float(norm1[2]) if len(norm1) > 2 else 1e-5
         self.eps2 = float(norm2[2]) if len(norm2) > 2 else 1e-5
-        lib = _lib.load()
-        if (self.stream.numel() != int(lib.smos_tfusion_layer_stream_floats(self.ffn, 1 if self.nq else 0)) or
-                self.params.numel() != int(lib.smos_tfusion_layer_param_floats(self.ffn))):
+        if (self.stream.numel() != _lib.query("smos_tfusion_layer_stream_floats", self.ffn, 1 if self.nq else 0) or
+                self.params.numel() != _lib.query("smos_tfusion_layer_param_floats", self.ffn)):
             raise RuntimeError("TfusionLayer: packed sizes disagree with the kernel's")
 
 
@@ -1471,14 +1410,12 @@ def tfusion_project(jobs):
             out = torch.empty((tk, cout), dtype=torch.float32, device=x.device)
         res.append(out)
         xs[j], pit[j], ws[j], outs[j], ops_[j], couts[j], toks[j] = x.data_ptr(), pitch, w.data_ptr(), out.data_ptr(), out.stride(0), cout, tk
-        bs[j] = bias.data_ptr() if bias is not None else None
-    lib = _lib.load()
+        bs[j] = _ptr(bias)
     x0 = jobs[0][0]
     label = ("tfusion_project[%s]" % ",".join("%dx128->%d" % (int(toks[j]), int(couts[j])) for j in range(n))
              if profiling.enabled() else None)
     with _on(x0.device), profiling.span(label):
-        rc = lib.smos_tfusion_project(n, xs, pit, ws, bs, outs, ops_, couts, toks, _stream(x0))
-    _lib.check(rc, "smos_tfusion_project")
+        _lib.call("smos_tfusion_project", n, xs, pit, ws, bs, outs, ops_, couts, toks, _stream(x0))
     return res
 
 
@@ -1497,12 +1434,9 @@ def tfusion_layer(sampled, query, prep, out=None):
     if to != tokens or out.shape[-1] != 128:
         raise RuntimeError("tfusion_layer: out must hold [tokens, 128]")
     nxt = torch.empty((tokens, prep.nq), dtype=torch.float32, device=sampled.device) if prep.nq else None
-    lib = _lib.load()
     with _on(sampled.device), profiling.span_f("tfusion_layer[%dx128x%d%s]", (tokens, prep.ffn, "+q%d" % prep.nq if prep.nq else "")):
-        rc = lib.smos_tfusion_layer(sampled.data_ptr(), query.data_ptr(), qp, prep.stream.data_ptr(), prep.params.data_ptr(),
-                                    out.data_ptr(), op, nxt.data_ptr() if nxt is not None else None, prep.nq, tokens, prep.ffn,
-                                    prep.eps1, prep.eps2, _stream(sampled))
-    _lib.check(rc, "smos_tfusion_layer")
+        _lib.call("smos_tfusion_layer", sampled.data_ptr(), query.data_ptr(), qp, prep.stream.data_ptr(), prep.params.data_ptr(),
+                  out.data_ptr(), op, _ptr(nxt), prep.nq, tokens, prep.ffn, prep.eps1, prep.eps2, _stream(sampled))
     return out, nxt
 
 
@@ -1567,14 +1501,12 @@ def tap_products_bf16x3(jobs):
             out = torch.empty((tk, cout), dtype=torch.float32, device=x.device)
         res.append(out)
         xs[j], pit[j], ws[j], outs[j], ops_[j], couts[j], toks[j] = x.data_ptr(), pitch, w.data_ptr(), out.data_ptr(), out.stride(0), cout, tk
-    lib = _lib.load()
     x0 = jobs[0][0]
     # the label of the fp32 form: bench.py's byte / FLOP model and profiles/label_durations.py price the launch as before
     label = ("tfusion_project[%s]" % ",".join("%dx128->%d" % (int(toks[j]), int(couts[j])) for j in range(n))
              if profiling.enabled() else None)
     with _on(x0.device), profiling.span(label):
-        rc = lib.smos_tap_products_bf16x3(n, xs, pit, ws, outs, ops_, couts, toks, _stream(x0))
-    _lib.check(rc, "smos_tap_products_bf16x3")
+        _lib.call("smos_tap_products_bf16x3", n, xs, pit, ws, outs, ops_, couts, toks, _stream(x0))
     return res
 
 
@@ -1658,11 +1590,10 @@ def upconv3x3(conv_a, bias, sources, act, out=None):
     b, c, ho, wo = conv_a.shape
     if out is None:
         out = conv_a
-    lib = _lib.load()
     st = _stream(conv_a)
     if not 1 <= len(sources) <= 2:
         raise RuntimeError("upconv3x3: one or two upsampled sources, got %d" % len(sources))
-    fused = _UPCONV_XY and all(lib.smos_upconv_xy_ok(src[0].shape[2], ho) for src in sources)
+    fused = _UPCONV_XY and all(_lib.query("smos_upconv_xy_ok", src[0].shape[2], ho) for src in sources)
     zs, ts = [], []
     pre = {}
     if _TAP_GEMM in ("tf", "x3"):
@@ -1703,23 +1634,21 @@ def upconv3x3(conv_a, bias, sources, act, out=None):
                 continue
             t = torch.empty((b, 3, hs, wo, c), dtype=torch.float32, device=conv_a.device)
             with profiling.span_f("upconv_xpass[%dx%dx%dx%d->%d]", (b, hs, ws, c, wo)):
-                _lib.check(lib.smos_upconv_xpass(z.data_ptr(), t.data_ptr(), b, hs, ws, c, wo, st), "smos_upconv_xpass")
+                _lib.call("smos_upconv_xpass", z.data_ptr(), t.data_ptr(), b, hs, ws, c, wo, st)
             ts.append((t, hs))
         if fused:
             z1, h1, w1 = zs[0]
             z2, h2, w2 = zs[1] if len(zs) > 1 else (None, 0, 0)
             with profiling.span("upconv_xy[%dx%dx%dx%d<-%s]" % (b, ho, wo, c, "+".join("%dx%d" % (h, w) for _, h, w in zs))
                                 if profiling.enabled() else None):
-                _lib.check(lib.smos_upconv_xy(conv_a.data_ptr(), _cl("upconv3x3", conv_a), bias.data_ptr(), z1.data_ptr(), h1, w1,
-                                              z2.data_ptr() if z2 is not None else None, h2, w2, out.data_ptr(), _cl("upconv3x3", out),
-                                              b, ho, wo, c, int(act), st), "smos_upconv_xy")
+                _lib.call("smos_upconv_xy", conv_a.data_ptr(), _cl("upconv3x3", conv_a), bias.data_ptr(), z1.data_ptr(), h1, w1,
+                          _ptr(z2), h2, w2, out.data_ptr(), _cl("upconv3x3", out), b, ho, wo, c, int(act), st)
             return out
         t1, h1 = ts[0]
         t2, h2 = ts[1] if len(ts) > 1 else (None, 0)
         with profiling.span_f("upconv_ypass[%dx%dx%dx%d]", (b, ho, wo, c)):
-            _lib.check(lib.smos_upconv_ypass(conv_a.data_ptr(), _cl("upconv3x3", conv_a), bias.data_ptr(), t1.data_ptr(), h1,
-                                             t2.data_ptr() if t2 is not None else None, h2, out.data_ptr(), _cl("upconv3x3", out),
-                                             b, ho, wo, c, int(act), st), "smos_upconv_ypass")
+            _lib.call("smos_upconv_ypass", conv_a.data_ptr(), _cl("upconv3x3", conv_a), bias.data_ptr(), t1.data_ptr(), h1,
+                      _ptr(t2), h2, out.data_ptr(), _cl("upconv3x3", out), b, ho, wo, c, int(act), st)
     return out
 
 
@@ -1737,9 +1666,9 @@ def upconv_xy_units(conv_a, bias, z1, z2, act, strip, max_blocks=0, out=None):
             raise RuntimeError("upconv_xy_units: tap products must be a contiguous [B*Hs*Ws, 9*C] matrix, got %s" % (tuple(z[0].shape),))
     (p1, h1, w1), (p2, h2, w2) = ((z[0].data_ptr(), z[1], z[2]) if z is not None else (None, 0, 0) for z in (z1, z2))
     with _on(conv_a.device):
-        _lib.check(_lib.load().smos_upconv_xy_units(conv_a.data_ptr(), _cl("upconv_xy_units", conv_a), bias.data_ptr(), p1, h1, w1, p2, h2, w2,
-                                                    out.data_ptr(), _cl("upconv_xy_units", out), b, ho, wo, c, int(act), int(strip),
-                                                    int(max_blocks), _stream(conv_a)), "smos_upconv_xy_units")
+        _lib.call("smos_upconv_xy_units", conv_a.data_ptr(), _cl("upconv_xy_units", conv_a), bias.data_ptr(), p1, h1, w1, p2, h2,
+                  w2, out.data_ptr(), _cl("upconv_xy_units", out), b, ho, wo, c, int(act), int(strip), int(max_blocks),
+                  _stream(conv_a))
     return out
 
 
@@ -1860,8 +1789,7 @@ def stem_plan(coord, h, w, row_floats=0):
     b, t, n, k = coord.shape[:4]
     dev = coord.device
     cells = b * h * w
-    lib = _lib.load()
-    words = int(lib.smos_stem_scan_state_words(cells))
+    words = _lib.query("smos_stem_scan_state_words", cells)
     if words < 0:
         raise RuntimeError("stem_plan: grid too large for the scan")
     flags = _stream_workspace("stem_flags", (cells,), torch.int32, dev, zero=True)      # left all-zero by the scan
@@ -1875,9 +1803,9 @@ def stem_plan(coord, h, w, row_floats=0):
         rows = _stream_workspace("stem_rows", (min(cells, b * t * n), row_floats), torch.float32, dev)
     st = _stream(coord)
     with _on(dev), profiling.span_f("stem_mark+scan[%dx%dx%d]", (b, h, w)):
-        _lib.check(lib.smos_stem_mark(coord.data_ptr(), k, b, t, n, h, w, flags.data_ptr(), state.data_ptr(), st), "smos_stem_mark")
-        _lib.check(lib.smos_stem_scan(flags.data_ptr(), b, h, w, state.data_ptr(), row_cell.data_ptr(), row_of.data_ptr(),
-                                      meta.data_ptr(), rows.data_ptr() if rows is not None else None, row_floats, st), "smos_stem_scan")
+        _lib.call("smos_stem_mark", coord.data_ptr(), k, b, t, n, h, w, flags.data_ptr(), state.data_ptr(), st)
+        _lib.call("smos_stem_scan", flags.data_ptr(), b, h, w, state.data_ptr(), row_cell.data_ptr(), row_of.data_ptr(),
+                  meta.data_ptr(), _ptr(rows), row_floats, st)
     return StemPlan(b, h, w, row_cell, row_of, meta, rows)
 
 
@@ -1886,8 +1814,7 @@ def pointnet_scatter_rows(xyzi, coord, w1, b1, w2, b2, plan, pts_out=None, n_liv
     this stream's scratch (valid until the next plan on the stream); only the first plan.meta[11] rows exist (zero-filled by
     the plan's scan) -- the dense grid is never materialised."""
     _require_cuda("pointnet_scatter_rows", xyzi, coord, w1, b1, w2, b2, pts_out, n_live)
-    if n_live is not None and (n_live.dtype != torch.int32 or n_live.numel() < 1):
-        raise RuntimeError("pointnet_scatter_rows: n_live must be a device int32 tensor")
+    live = _live_ptr("pointnet_scatter_rows", n_live)
     b, t, cin, n = xyzi.shape[:4]
     k = coord.shape[3]
     if not (xyzi.is_contiguous() and coord.is_contiguous()):
@@ -1899,16 +1826,12 @@ def pointnet_scatter_rows(xyzi, coord, w1, b1, w2, b2, plan, pts_out=None, n_liv
     po_b = po_n = 0
     if pts_out is not None:
         po_b, po_n = _rows("pointnet_scatter_rows", pts_out, cout)
-    lib = _lib.load()
     st = _stream(xyzi)
     # the span holds exactly ONE kernel, so its HIP-event mean is comparable with rocprofv3's per-kernel mean
     with _on(xyzi.device), profiling.span_f("pointnet_scatter[%dx%dx%d->%dx%d]", (b, t, n, plan.h, plan.w)):
-        rc = lib.smos_pointnet_scatter_rows_live(xyzi.data_ptr(), coord.data_ptr(), k, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                                                 b2.data_ptr(), rows.data_ptr(), plan.row_of.data_ptr(),
-                                                 pts_out.data_ptr() if pts_out is not None else None, po_b, po_n, b, t, n,
-                                                 plan.h, plan.w, cin, w1.shape[0], cout,
-                                                 n_live.data_ptr() if n_live is not None else None, st)
-    _lib.check(rc, "smos_pointnet_scatter_rows_live")
+        _lib.call("smos_pointnet_scatter_rows", xyzi.data_ptr(), coord.data_ptr(), k, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                  b2.data_ptr(), rows.data_ptr(), plan.row_of.data_ptr(), _ptr(pts_out), po_b, po_n, b, t, n, plan.h, plan.w, cin,
+                  w1.shape[0], cout, live, st)
     return rows
 
 
@@ -1932,16 +1855,15 @@ def sparse_downsample(src, plan, wprep, bias, compact, out=None):
         out = empty_cl(b, cout, (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1, dev)
     y_ptrs = (ctypes.c_void_p * 4)(*[y.data_ptr() for y in ys])
     w_ptrs = (ctypes.c_void_p * 4)(*[wt.data_ptr() for wt in wprep])
-    lib = _lib.load()
     st = _stream(src)
     tag = "[%dx%dx%dx%d]" % (b, h, w, cin) if profiling.enabled() else ""
     with _on(dev):
         with profiling.span("stem_gemm" + tag):
-            _lib.check(lib.smos_stem_gemm(src.data_ptr(), None if compact else plan.row_cell.data_ptr(), plan.meta.data_ptr(),
-                                          w_ptrs, y_ptrs, cin, cout, st), "smos_stem_gemm")
+            _lib.call("smos_stem_gemm", src.data_ptr(), None if compact else plan.row_cell.data_ptr(), plan.meta.data_ptr(), w_ptrs,
+                      y_ptrs, cin, cout, st)
         with profiling.span("stem_epilogue" + tag):
-            _lib.check(lib.smos_stem_epilogue(y_ptrs, plan.meta.data_ptr(), plan.row_of.data_ptr(), bias.data_ptr(), out.data_ptr(),
-                                              _cl("sparse_downsample", out), b, h, w, cout, st), "smos_stem_epilogue")
+            _lib.call("smos_stem_epilogue", y_ptrs, plan.meta.data_ptr(), plan.row_of.data_ptr(), bias.data_ptr(), out.data_ptr(),
+                      _cl("sparse_downsample", out), b, h, w, cout, st)
     return out
 
 
@@ -2050,13 +1972,10 @@ def bias_act_cl(x, bias, act, out=None, residual=None):
     b, c, h, w = x.shape
     if out is None:
         out = empty_cl(b, c, h, w, x.device)
-    lib = _lib.load()
     with _on(x.device):
-        rc = lib.smos_bias_act_cl(x.data_ptr(), _cl("bias_act_cl", x), bias.data_ptr() if bias is not None else None,
-                                  residual.data_ptr() if residual is not None else None,
-                                  _cl("bias_act_cl", residual) if residual is not None else 0, out.data_ptr(),
-                                  _cl("bias_act_cl", out), b * h * w, c, act, _stream(x))
-    _lib.check(rc, "smos_bias_act_cl")
+        _lib.call("smos_bias_act_cl", x.data_ptr(), _cl("bias_act_cl", x), _ptr(bias), _ptr(residual),
+                  _cl("bias_act_cl", residual) if residual is not None else 0, out.data_ptr(), _cl("bias_act_cl", out), b * h * w,
+                  c, act, _stream(x))
     return out
 
 
@@ -2065,12 +1984,10 @@ def downsample_epilogue_cl(a, p, bias, stride, out=None):
     b, c, h, w = p.shape
     if out is None:
         out = empty_cl(b, c, a.shape[2], a.shape[3], a.device)
-    lib = _lib.load()
     with _on(a.device):
-        rc = lib.smos_downsample_epilogue_cl(a.data_ptr(), _cl("downsample_epilogue_cl", a), p.data_ptr(),
-                                             _cl("downsample_epilogue_cl", p), bias.data_ptr(), out.data_ptr(),
-                                             _cl("downsample_epilogue_cl", out), b, c, h, w, stride, _stream(a))
-    _lib.check(rc, "smos_downsample_epilogue_cl")
+        _lib.call("smos_downsample_epilogue_cl", a.data_ptr(), _cl("downsample_epilogue_cl", a), p.data_ptr(),
+                  _cl("downsample_epilogue_cl", p), bias.data_ptr(), out.data_ptr(), _cl("downsample_epilogue_cl", out), b, c, h, w,
+                  stride, _stream(a))
     return out
 
 
@@ -2099,12 +2016,10 @@ def downsample_pool_branch(x, wpairs, a, bias, stride, out=None):
         out = empty_cl(b, c, ho, wo, x.device)
     elif tuple(out.shape) != (b, c, ho, wo):
         raise RuntimeError("downsample_pool_branch: out has shape %s" % (tuple(out.shape),))
-    lib = _lib.load()
     with _on(x.device), profiling.span_f("downsample_pool_branch[%dx%dx%dx%d/s%d]", (b, c, h, w, stride)):
-        rc = lib.smos_downsample_pool_branch(x.data_ptr(), _cl("downsample_pool_branch", x), wpairs.data_ptr(), a.data_ptr(),
-                                             _cl("downsample_pool_branch", a), bias.data_ptr(), out.data_ptr(),
-                                             _cl("downsample_pool_branch", out), b, h, w, c, c, int(stride), _stream(x))
-    _lib.check(rc, "smos_downsample_pool_branch")
+        _lib.call("smos_downsample_pool_branch", x.data_ptr(), _cl("downsample_pool_branch", x), wpairs.data_ptr(), a.data_ptr(),
+                  _cl("downsample_pool_branch", a), bias.data_ptr(), out.data_ptr(), _cl("downsample_pool_branch", out), b, h, w, c,
+                  c, int(stride), _stream(x))
     return out
 
 
@@ -2113,14 +2028,11 @@ def channel_gate_residual_cl(y, bias, w1, b1, w2, b2, xres, ws, out=None):
     b, c, h, w = y.shape
     if out is None:
         out = empty_cl(b, c, h, w, y.device)
-    lib = _lib.load()
     with _on(y.device):
-        rc = lib.smos_channel_gate_residual_cl(y.data_ptr(), _cl("channel_gate_residual_cl", y), bias.data_ptr(), w1.data_ptr(),
-                                               b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), xres.data_ptr(),
-                                               _cl("channel_gate_residual_cl", xres), out.data_ptr(),
-                                               _cl("channel_gate_residual_cl", out), ws.data_ptr(), ws.numel(), b, c, w1.shape[0],
-                                               h * w, _stream(y))
-    _lib.check(rc, "smos_channel_gate_residual_cl")
+        _lib.call("smos_channel_gate_residual_cl", y.data_ptr(), _cl("channel_gate_residual_cl", y), bias.data_ptr(), w1.data_ptr(),
+                  b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), xres.data_ptr(), _cl("channel_gate_residual_cl", xres),
+                  out.data_ptr(), _cl("channel_gate_residual_cl", out), ws.data_ptr(), ws.numel(), b, c, w1.shape[0], h * w,
+                  _stream(y))
     return out
 
 
@@ -2133,14 +2045,11 @@ def channel_gate_apply_cl(y, bias, w1, b1, w2, b2, xres, chan_sums, gate_ws, out
         raise RuntimeError("channel_gate_apply_cl: chan_sums must be contiguous [B, chunks, C] and gate_ws hold B*C floats")
     if out is None:
         out = empty_cl(b, c, h, w, y.device)
-    lib = _lib.load()
     with _on(y.device):
-        rc = lib.smos_channel_gate_apply_cl(y.data_ptr(), _cl("channel_gate_apply_cl", y), bias.data_ptr(), w1.data_ptr(),
-                                            b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), xres.data_ptr(),
-                                            _cl("channel_gate_apply_cl", xres), out.data_ptr(), _cl("channel_gate_apply_cl", out),
-                                            chan_sums.data_ptr(), chan_sums.shape[1], gate_ws.data_ptr(), b, c, w1.shape[0], h * w,
-                                            _stream(y))
-    _lib.check(rc, "smos_channel_gate_apply_cl")
+        _lib.call("smos_channel_gate_apply_cl", y.data_ptr(), _cl("channel_gate_apply_cl", y), bias.data_ptr(), w1.data_ptr(),
+                  b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), xres.data_ptr(), _cl("channel_gate_apply_cl", xres), out.data_ptr(),
+                  _cl("channel_gate_apply_cl", out), chan_sums.data_ptr(), chan_sums.shape[1], gate_ws.data_ptr(), b, c,
+                  w1.shape[0], h * w, _stream(y))
     return out
 
 
@@ -2151,14 +2060,11 @@ def upsample_concat_cl(sources, size):
     ctot = sum(s.shape[1] for s in sources)
     out = empty_cl(b, ctot, size[0], size[1], sources[0].device)
     ptrs = (ctypes.c_void_p * len(sources))(*[s.data_ptr() for s in sources])
-    lib = _lib.load()
     with _on(out.device):
-        rc = lib.smos_upsample_concat_cl(ptrs, _lib.i64_array([s.shape[1] for s in sources]),
-                                         _lib.i64_array([s.shape[2] for s in sources]),
-                                         _lib.i64_array([s.shape[3] for s in sources]),
-                                         _lib.i64_array([_cl("upsample_concat_cl", s) for s in sources]), len(sources),
-                                         out.data_ptr(), b, size[0], size[1], _stream(out))
-    _lib.check(rc, "smos_upsample_concat_cl")
+        _lib.call("smos_upsample_concat_cl", ptrs, _lib.i64_array([s.shape[1] for s in sources]),
+                  _lib.i64_array([s.shape[2] for s in sources]), _lib.i64_array([s.shape[3] for s in sources]),
+                  _lib.i64_array([_cl("upsample_concat_cl", s) for s in sources]), len(sources), out.data_ptr(), b, size[0],
+                  size[1], _stream(out))
     return out
 
 
@@ -2175,9 +2081,7 @@ def zero_views_cl(views):
             raise RuntimeError("zero_views_cl: float32 views on one device")
         ptrs[i], rows[i], rf[i], pit[i] = v.data_ptr(), b * h * w, c, _cl("zero_views_cl", v)
     with _on(views[0].device):
-        rc = _lib.load().smos_zero_views_cl(k, ptrs, rows, rf, pit, _stream(views[0]))
-    if rc:
-        _lib.check(rc, "smos_zero_views_cl")
+        _lib.call("smos_zero_views_cl", k, ptrs, rows, rf, pit, _stream(views[0]))
 
 
 def _coord_view(name, t, b, n):
@@ -2199,27 +2103,23 @@ def gather_scatter_cl(grid, gcoord, gscale, scoord=None, sscale=None, out=None, 
     cell whose members are all negative stays 0, where VoxelMaxPool keeps the true maximum -- and is meant for the engine's
     non-negative maps; the point rows carry the signed gathered values."""
     _require_cuda("gather_scatter_cl", grid, gcoord, scoord, out, pts_out, n_live)
-    if n_live is not None and (n_live.dtype != torch.int32 or n_live.numel() < 1):
-        raise RuntimeError("gather_scatter_cl: n_live must be a device int32 tensor")
+    live = _live_ptr("gather_scatter_cl", n_live)
     b, c, hg, wg = grid.shape
     n = gcoord.shape[1]
     kg, gbs = _coord_view("gather_scatter_cl", gcoord, b, None)
     ho = wo = ks = op = sbs = 0
+    sc = ss = None                        # the scatter's coordinates and scale: only with a target
     if out is not None:
         ho, wo, op = out.shape[2], out.shape[3], _cl("gather_scatter_cl", out)
         ks, sbs = _coord_view("gather_scatter_cl", scoord, b, n)
+        sc, ss = scoord.data_ptr(), _lib.f32_array(sscale)
     po_b = po_n = 0
     if pts_out is not None:
         po_b, po_n = _rows("gather_scatter_cl", pts_out, c)
-    lib = _lib.load()
     label = ("gather_scatter_cl[%dx%dx%dx%d->%d->%dx%d%s]" % (b, c, hg, wg, n, ho, wo,
                                                            "+pts" if pts_out is not None and out is not None else "")
              if profiling.enabled() else None)
     with _on(grid.device), profiling.span(label):
-        rc = lib.smos_gather_scatter_cl_view(grid.data_ptr(), _cl("gather_scatter_cl", grid), gcoord.data_ptr(), kg, gbs,
-                                             _lib.f32_array(gscale), scoord.data_ptr() if out is not None else None, ks, sbs,
-                                             _lib.f32_array(sscale) if out is not None else None,
-                                             out.data_ptr() if out is not None else None, op,
-                                             pts_out.data_ptr() if pts_out is not None else None, po_b, po_n, b, c, hg, wg, n, ho, wo,
-                                             n_live.data_ptr() if n_live is not None else None, _stream(grid))
-    _lib.check(rc, "smos_gather_scatter_cl_view")
+        _lib.call("smos_gather_scatter_cl", grid.data_ptr(), _cl("gather_scatter_cl", grid), gcoord.data_ptr(), kg, gbs,
+                  _lib.f32_array(gscale), sc, ks, sbs, ss, _ptr(out), op, _ptr(pts_out), po_b, po_n, b, c, hg, wg, n, ho, wo, live,
+                  _stream(grid))

@@ -565,7 +565,7 @@ def test_gather_scatter_cl_float4_lanes_equal_the_one_lane_per_channel_kernel(c,
 
 
 def test_gather_scatter_cl_takes_strided_coordinate_views_and_zero_views_fills_slices():
-    """smos_gather_scatter_cl_view: the coordinates as slices of the reference's [B, T, N, 3, 1] / [B, T, N, 2, 1] tensors (pitch 3,
+    """smos_gather_scatter_cl: the coordinates as slices of the reference's [B, T, N, 3, 1] / [B, T, N, 2, 1] tensors (pitch 3,
     batch stride T * N * 3) give what their compacted copies give, bit for bit.  smos_zero_views_cl: a dense map and a channel slice
     of a wider one zeroed in one launch, the other half of the wide map untouched."""
     gen = torch.Generator(device="cpu").manual_seed(47)
@@ -1258,7 +1258,7 @@ def test_downsample_pool_branch_against_float64_and_the_two_launch_form(c, hw, s
 
 @pytest.mark.parametrize("n_live", [0, 1, 31, 32, 1000, 2047, 2048, 5000])
 def test_point_head_and_gathers_leave_the_padding_tail_out(n_live):
-    """The `_live` entry points (smos_point_head_live, smos_gather_scatter_cl_live; include/smos.h): given a DEVICE-side count of
+    """The `n_live` argument (smos_point_head, smos_gather_scatter_cl; include/smos.h): given a DEVICE-side count of
     the real points at the front of every sample they produce the same values for those points, bit for bit, and zeros / nothing
     for the tail [n_live, N) -- for counts of 0, inside a tile, at tile borders, N and beyond N (clamped)."""
     gen = torch.Generator(device="cpu").manual_seed(151)

@@ -1,4 +1,4 @@
-"""The point head that gathers the decoder's BEV rows itself (smos_point_head_gather_live, csrc/point_head.hip) against the
+"""The point head that gathers the decoder's BEV rows itself (smos_point_head_gather, csrc/point_head.hip) against the
 two launches it replaces, against float64, and inside the engine; and the layer-1 operand order both forms share."""
 import pytest
 import torch

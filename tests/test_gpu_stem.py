@@ -229,7 +229,7 @@ def test_point_scatter_persistent_loop(cap, trips):
 @pytest.mark.parametrize("cap", [0, 1])
 @pytest.mark.parametrize("n_live", [0, 1, 31, 32, 33, 1012, 1013, 1020])
 def test_point_scatter_rows_n_live(n_live, cap):
-    """smos_pointnet_scatter_rows_live: a DEVICE count of the real points at the front of the current (t == 0) scans; the tail
+    """smos_pointnet_scatter_rows: a DEVICE count of the real points at the front of the current (t == 0) scans; the tail
     [k, N) of those scans sits at -4864.0 (outside every grid: the runner's contract).  The row table does not depend on the
     count; the point rows of the real points are the same bits; and a 32-point tile that starts at or after k -- whose points
     are all outside -- is skipped even in frame 0, so its point rows are not written (point_fused.hip: a tile is skipped unless

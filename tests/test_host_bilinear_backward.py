@@ -1,8 +1,6 @@
 """Backward of the bilinear gather without a GPU: the float64 reference of tests/bilinear_bwd_cases.py against torch's CPU
 autograd of F.grid_sample, the C ABI of smos_bilinear_gather_bwd, and the refusal of a coordinate gradient."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,8 +10,8 @@ import torch.nn.functional as F
 from oracle import ops_np
 from streammos_amd import _lib, ops
 from tests import bilinear_bwd_cases as cases
+from tests import util
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "smos_bilinear_gather_bwd"
 
 
@@ -89,14 +87,13 @@ def test_grid_stride_case_has_more_tiles_than_waves_and_whole_tiles_of_padding()
 
 
 def test_header_declares_and_library_exports_the_backward():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "smos.h")).read(), flags=re.S)
-    declared = {m.group(1): m.group(2) for m in re.finditer(r"\b(smos_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
+    declared = util.header_declarations()
     assert NAME in declared
     lib = ctypes.CDLL(_lib.LIB_PATH)          # loads without a GPU; no compute call is made
     assert hasattr(lib, NAME)
-    args = [a for a in declared[NAME].split(",") if a.strip()]
+    args = declared[NAME][1]
     assert len(_lib.SIGNATURES[NAME]) == len(args) == len(_lib.SIGNATURES["smos_bilinear_gather_fwd"])
-    assert "#define SMOS_ABI_VERSION 1" in text and _lib.ABI_VERSION == 1
+    assert util.header_abi_version() == _lib.ABI_VERSION
 
 
 def test_coordinate_gradient_is_refused():

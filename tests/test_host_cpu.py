@@ -3,7 +3,6 @@ interface, the CPU twin of VoxelMaxPool, sequence sharding (incl. a world_size-2
 import ctypes
 import json
 import os
-import re
 import subprocess
 import sys
 
@@ -13,15 +12,14 @@ import torch
 
 from streammos_amd import _lib, preprocess, streaming, synth
 from tests import cases
+from tests import util
 from tests.util import check_inputs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _declared(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(smos_[a-z0-9_]+)\s*\(", text)))
+    return sorted(util.header_declarations(header))
 
 
 def test_hip_library_exports_every_declared_symbol():
@@ -31,7 +29,7 @@ def test_hip_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), n
     assert set(names) == set(_lib.SIGNATURES) | {"smos_last_error"}
-    assert lib.smos_abi_version() == 1
+    assert lib.smos_abi_version() == _lib.ABI_VERSION == util.header_abi_version()
 
 
 def test_cpu_library_exports_every_declared_symbol():

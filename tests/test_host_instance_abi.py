@@ -1,23 +1,15 @@
 """The C ABI of the device-resident instance vote (include/smos.h, libsmos_hip.so, streammos_amd._lib): declared, exported,
 bound with the declared argument counts, and the workspace query -- host code only, no GPU."""
 import ctypes
-import os
-import re
 
 from streammos_amd import _lib
+from tests import util
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("smos_instance_work_bytes", "smos_instance_cluster", "smos_box_vote_dev", "smos_instance_apply")
 
 
-def _declarations():
-    text = open(os.path.join(ROOT, "include", "smos.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(smos_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
-
-
 def test_header_declares_and_library_exports_the_entry_points():
-    declared = _declarations()
+    declared = util.header_declarations()
     lib = ctypes.CDLL(_lib.LIB_PATH)          # loads without a GPU; no compute call is made
     for name in NEW:
         assert name in declared, name
@@ -25,14 +17,13 @@ def test_header_declares_and_library_exports_the_entry_points():
 
 
 def test_bindings_have_the_declared_argument_counts():
-    declared = _declarations()
+    declared = util.header_declarations()
     for name in NEW:
-        args = [a for a in declared[name].split(",") if a.strip() and a.strip() != "void"]
+        args = declared[name][1]
         assert len(_lib.SIGNATURES[name]) == len(args), (name, len(_lib.SIGNATURES[name]), len(args))
     # every other binding too: the header is the one place the argument lists are written down
     for name, argtypes in _lib.SIGNATURES.items():
-        args = [a for a in declared[name].split(",") if a.strip() and a.strip() != "void"]
-        assert len(argtypes) == len(args), name
+        assert len(argtypes) == len(declared[name][1]), name
 
 
 def test_work_bytes_is_positive_and_monotonic():

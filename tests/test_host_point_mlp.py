@@ -2,8 +2,6 @@
 float64 modules on the CPU, the six value-only mutants of it against the GPU test's bar, and the host side of the new
 entry points (switch, bindings, work-space query).  No GPU."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -11,8 +9,8 @@ import torch
 
 from streammos_amd import _lib, ops
 from tests import point_mlp_cases as cases
+from tests import util
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("smos_point_mlp_chunk", "smos_point_mlp_fold_floats", "smos_point_mlp_stat_doubles", "smos_point_mlp_work_bytes",
        "smos_point_mlp_fwd", "smos_point_mlp_bwd")
 
@@ -107,13 +105,11 @@ def test_switch_on_keeps_cpu_and_float64_inputs_on_the_module_path():
 
 
 def test_header_library_and_signatures_agree():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "smos.h")).read(), flags=re.S)
-    declared = {m.group(1): m.group(2) for m in re.finditer(r"\b(smos_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
+    declared = util.header_declarations()
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW:
         assert name in declared and hasattr(lib, name) and name in _lib.SIGNATURES
-        args = [a for a in declared[name].split(",") if a.strip() and a.strip() != "void"]
-        assert len(_lib.SIGNATURES[name]) == len(args), name
+        assert len(_lib.SIGNATURES[name]) == len(declared[name][1]), name
 
 
 def test_work_space_query_and_the_python_refusals():

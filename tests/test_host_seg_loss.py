@@ -3,7 +3,6 @@ against torch's CPU autograd of refapi/models/losses.py, the closed-form Lovasz 
 float32 restatement of the kernels against the derived bounds, the sort-key mapping, the C ABI and the refusals."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import torch
 from streammos_amd import _lib, engine, ops
 from streammos_amd.refapi.models import losses
 from tests import loss_cases as cases
+from tests import util
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -181,13 +181,11 @@ def test_cases_cover_what_they_are_named_for():
 
 
 def test_header_declares_and_library_exports_the_loss():
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "smos.h")).read(), flags=re.S)
-    declared = {m.group(1): m.group(2) for m in re.finditer(r"\b(smos_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)}
+    declared = util.header_declarations()
     lib = ctypes.CDLL(_lib.LIB_PATH)          # loads without a GPU; no compute call is made
     for name in ("smos_seg_loss_tile", "smos_seg_loss_work_bytes", "smos_seg_loss_fwd", "smos_seg_loss_bwd"):
         assert name in declared and hasattr(lib, name)
-        args = [a for a in declared[name].split(",") if a.strip() and a.strip() != "void"]
-        assert len(_lib.SIGNATURES[name]) == len(args), name
+        assert len(_lib.SIGNATURES[name]) == len(declared[name][1]), name
     assert lib.smos_seg_loss_tile() == cases.TILE
     lib.smos_seg_loss_work_bytes.restype = ctypes.c_int64
     lib.smos_seg_loss_work_bytes.argtypes = [ctypes.c_int64, ctypes.c_int32]

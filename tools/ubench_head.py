@@ -30,7 +30,7 @@ b.record(); torch.cuda.synchronize()
 ms = a.elapsed_time(b) / 30
 print("point_head, 96 069 live points per sample: %.4f ms  (matrix floor %.4f ms)" % (ms, 0.2015 * 96069 / 160000))
 
-# fold mode: smos_point_head_gather_live against gather_scatter_cl(pts_out=rows[:, :, 64:128]) + point_head
+# fold mode: smos_point_head_gather against gather_scatter_cl(pts_out=rows[:, :, 64:128]) + point_head
 grid = torch.randn((4, 256, 256, 64), generator=g).to(dev).permute(0, 3, 1, 2)
 pcds = torch.full((4, 3, 160000, 3, 1), -1000.0)
 pcds[:, :, :96069, :2, 0] = torch.rand((4, 3, 96069, 2), generator=g) * 511.0      # positions = coordinate * 0.5 over the map
