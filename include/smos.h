@@ -41,7 +41,7 @@ int smos_abi_version(void);
 const char* smos_last_error(void);
 /* Test hook (process-wide, not part of the data path; the one piece of state the library keeps): caps the grid of the
  * persistent convolution kernels (smos_conv_cl / _rows_cl / _wino_cl / _wino1d_cl / _bf16_cl), of smos_stem_gemm, of
- * smos_pointnet_scatter / _rows, of smos_gather_scatter_cl and of the emit, copy, start and sum
+ * smos_pointnet_scatter / _rows, of smos_gather_scatter_cl, of smos_point_head / _gather, of smos_tta_argmax and of the emit, copy, start and sum
  * kernels of smos_bilinear_gather_bwd_det / smos_msda_bwd_det and of smos_train_prep_build / _draws and smos_copy_paste_* at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
  * item-boundary code paths, a wave's whole-tile / head / tail units of the stem, the scatter's software pipeline -- on shapes
  * small enough to check against float64.  The results do not depend on it. */

@@ -244,8 +244,8 @@ static int launch_point_head(HeadArgs a, int64_t K1, int64_t M1, int64_t M2, smo
   const int cus = ks.cus;
   const int64_t tiles = (int64_t)a.B * ((a.N + 31) / 32);
   const int64_t want = (tiles + 7) / 8;
-  hipLaunchKernelGGL(point_head<kGather>, dim3((unsigned)(want < cus ? want : cus)), dim3(kHeadBlock), kHeadLds * sizeof(float),
-                     (hipStream_t)stream, a);
+  const int64_t blocks = conv_grid_cap(want < cus ? want : cus);   // (the test hook's cap: several tiles per wave)
+  hipLaunchKernelGGL(point_head<kGather>, dim3((unsigned)blocks), dim3(kHeadBlock), kHeadLds * sizeof(float), (hipStream_t)stream, a);
   return check_launch("point_head");
 }
 

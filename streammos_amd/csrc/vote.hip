@@ -264,6 +264,7 @@ extern "C" int smos_tta_argmax(const float* pred, int64_t B, int64_t K, int64_t 
   SMOS_REQUIRE(B > 0 && K > 0 && K <= 8 && N >= 0, "tta_argmax: bad sizes (B=%lld K=%lld)", (long long)B, (long long)K);
   if (N == 0) return SMOS_OK;
   SMOS_REQUIRE(pred && labels, "tta_argmax: null device pointer");
-  hipLaunchKernelGGL(tta_argmax, dim3(grid_for(N)), dim3(kBlock), 0, (hipStream_t)stream, pred, (int)B, (int)K, N, labels, prob);
+  hipLaunchKernelGGL(tta_argmax, dim3((unsigned)conv_grid_cap(grid_for(N))), dim3(kBlock), 0, (hipStream_t)stream, pred, (int)B, (int)K, N,
+                     labels, prob);
   return check_launch("tta_argmax");
 }
