@@ -731,6 +731,46 @@ int smos_point_mlp_bwd(const float* x, const float* grad_y, int64_t S, int64_t N
                        const double* eps_mom, const float* fold, const double* dstat, void* const* grads, void* work,
                        int64_t work_bytes, smos_stream_t stream);
 
+/* Training point head (csrc/point_head_train.hip): cat(a, b, c) -> dropout -> conv1x1 192->96 -> BN1 -> ReLU ->
+ * conv1x1 96->64 -> BN2 -> ReLU -> dropout -> conv1x1 64->3 + bias (CatFusion + PredBranch) on three [B,64,N] channel-major float32
+ * inputs -> logits [B,3,N] float32.
+ *   pitch      HOST array of 3: floats between two channels of a / b / c (>= N; a sample is 64 channels).  Outputs are dense.
+ *   masks      smos_point_head_train_mask_words(B*N) uint32 of packed keep bits, 8 word planes of B*N: bit k & 31 of word k >> 5
+ *              keeps input channel k (k < 192), bit j & 31 of word 6 + (j >> 5) keeps channel j of the second dropout.  NULL:
+ *              nothing is dropped and nothing scaled.  scale = 1 / keep probability (1.25), applied to kept values only.
+ *   smos_point_head_train_masks fills them: from keep1 [B,192,N] and keep2 [B,64,N] bytes (non-zero: keep) when both are
+ *              given, else from Philox4x32-10 keyed by the two DEVICE int64 words at seed (read on the device): key = the
+ *              halves of seed[0], counter (point, 8 * word + i, halves of seed[1]); output v of call i decides bit 4 i + v; a
+ *              value is kept iff its 32-bit draw is below 3435973837 = ceil(0.8 * 2^32): keep probability 0.8 + 4.7e-11.
+ *   params     HOST array of 12 DEVICE float pointers: W1 [96,192], gamma1, beta1, running_mean1, running_var1, W2 [64,96],
+ *              gamma2, beta2, running_mean2, running_var2, W3 [3,64], b3
+ *   eps_mom    HOST array of 4 doubles: eps of BN1, BN2, then momentum of BN1, BN2
+ *   training   != 0: batch statistics over the B*N points (biased variance), the four running buffers updated in place
+ *              (running_var with the unbiased variance); B*N must exceed 1.  0: the running buffers are the statistics.
+ *   fold       smos_point_head_train_fold_floats() floats written by the forward and read by the backward (the weights as
+ *              the forward saw them and the folded statistics); with the inputs and the masks it is all the backward needs.  dstat: smos_point_head_train_stat_doubles() doubles, the float64 mean
+ *              and biased variance of both batch norms as the forward normalised with them.
+ *   grads      HOST array of 11 DEVICE float pointers, NULL where no gradient is wanted: d_a, d_b, d_c [B,64,N] (all three or
+ *              none), dW1, dgamma1, dbeta1, dW2, dgamma2, dbeta2, dW3, db3.  Work that only a NULL entry needs is not done.
+ *   work       smos_point_head_train_work_bytes(B*N) bytes of device scratch (-1 from the queries: too many points).
+ * Every sum over points is formed per chunk of smos_point_head_train_chunk() points and added in chunk order in float64: the bits
+ * of every result depend on the data alone, not on the grid (smos_debug_set_conv_grid_cap bounds the grids of the chunk walks)
+ * or the run.  Nothing is read back to the host. */
+int32_t smos_point_head_train_chunk(void);
+int32_t smos_point_head_train_fold_floats(void);
+int32_t smos_point_head_train_stat_doubles(void);
+int64_t smos_point_head_train_work_bytes(int64_t P);
+int64_t smos_point_head_train_mask_words(int64_t P);
+int smos_point_head_train_masks(const uint8_t* keep1, const uint8_t* keep2, const int64_t* seed, int64_t B, int64_t N,
+                                uint32_t* masks, smos_stream_t stream);
+int smos_point_head_train_fwd(const float* a, const float* b, const float* c, const int64_t* pitch, const uint32_t* masks,
+                              double scale, int64_t B, int64_t N, int32_t training, const void* const* params,
+                              const double* eps_mom, float* logits, float* fold, double* dstat, void* work, int64_t work_bytes,
+                              smos_stream_t stream);
+int smos_point_head_train_bwd(const float* a, const float* b, const float* c, const int64_t* pitch, const uint32_t* masks,
+                              double scale, const float* grad_logits, int64_t B, int64_t N, int32_t training, const float* fold,
+                              void* const* grads, void* work, int64_t work_bytes, smos_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,14 @@ SIGNATURES = {
     "smos_point_mlp_work_bytes": [i64],
     "smos_point_mlp_fwd": [vp, i64, i64, i32, ctypes.POINTER(vp), c_f64p, vp, vp, vp, vp, i64, vp],
     "smos_point_mlp_bwd": [vp, vp, i64, i64, i32, ctypes.POINTER(vp), c_f64p, vp, vp, ctypes.POINTER(vp), vp, i64, vp],
+    "smos_point_head_train_chunk": [],
+    "smos_point_head_train_fold_floats": [],
+    "smos_point_head_train_stat_doubles": [],
+    "smos_point_head_train_work_bytes": [i64],
+    "smos_point_head_train_mask_words": [i64],
+    "smos_point_head_train_masks": [vp, vp, vp, i64, i64, vp, vp],
+    "smos_point_head_train_fwd": [vp, vp, vp, c_i64p, vp, ctypes.c_double, i64, i64, i32, ctypes.POINTER(vp), c_f64p, vp, vp, vp, vp, i64, vp],
+    "smos_point_head_train_bwd": [vp, vp, vp, c_i64p, vp, ctypes.c_double, vp, i64, i64, i32, vp, ctypes.POINTER(vp), vp, i64, vp],
 }
 
 # the entries that return int64_t; every other one returns int (a status, or a small count)
@@ -119,6 +127,7 @@ INT64_RESULTS = (
     "smos_instance_work_bytes", "smos_stem_scan_state_words", "smos_point_head_weight_floats", "smos_conv_cl_sum_chunks",
     "smos_conv_wino_sum_chunks", "smos_basic_block_ws_floats", "smos_tfusion_layer_param_floats", "smos_tfusion_layer_stream_floats",
     "smos_train_prep_work_bytes", "smos_copy_paste_work_bytes", "smos_point_mlp_work_bytes",
+    "smos_point_head_train_work_bytes", "smos_point_head_train_mask_words",
 )
 
 ABI_VERSION = 2      # SMOS_ABI_VERSION of the include/smos.h these signatures were written against

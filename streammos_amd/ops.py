@@ -482,6 +482,193 @@ def point_mlp_train(x, bn0, conv1, bn1, conv2, bn2, training=None):
     return y
 
 
+_point_head_fused = None
+
+
+def set_point_head_fused(flag):
+    """Explicit setting of ``point_head_fused`` (True / False), or None to hand the decision back to the environment.
+    Returns the previous explicit setting."""
+    global _point_head_fused
+    prev, _point_head_fused = _point_head_fused, (None if flag is None else bool(flag))
+    return prev
+
+
+def point_head_fused():
+    """Whether ``backbone.point_head`` (refapi/networks/backbone.py) may route a supported CatFusion + PredBranch pair to
+    ``point_head_train``: the ``set_point_head_fused`` setting if there is one, else ``SMOS_POINT_HEAD_TRAIN`` in the
+    environment (default 0), read per call."""
+    if _point_head_fused is not None:
+        return _point_head_fused
+    return os.environ.get("SMOS_POINT_HEAD_TRAIN", "0").strip().lower() not in ("", "0", "false", "off", "no")
+
+
+def point_head_train_chunk():
+    """Points per chunk of partial sums of ``point_head_train`` (tests place their shapes around it)."""
+    return _lib.query("smos_point_head_train_chunk")
+
+
+def _point_head_pitch(x):
+    """floats between two channels of a [B,64,N,1] input the kernels can read in place, else None: points unit-strided, the
+    channels of a sample and the samples equally spaced (a dense tensor, or one cut out of a longer point axis)."""
+    b, c, n = x.shape[:3]
+    sb, sc, sn = x.stride()[:3]
+    pitch = sc if n > 1 or c > 1 else n
+    if (n > 1 and sn != 1) or pitch < n or (b > 1 and sb != c * pitch):
+        return None
+    return pitch
+
+
+class _PointHeadTrain(torch.autograd.Function):
+    """ops.point_head_train: one foreign call per direction.  Kept for the backward: the three inputs, the packed keep bits
+    (32 bytes per point) and the folded block (weights as the forward saw them and the statistics) -- no activation."""
+
+    @staticmethod
+    def forward(ctx, a, b, c, w1, g1, b1, w2, g2, b2, w3, bias3, buffers, eps_mom, training, masks, scale):
+        bs, _, n = a.shape[:3]
+        dev = a.device
+        need = _lib.query("smos_point_head_train_work_bytes", bs * n)
+        work = _stream_workspace("point_head_train", (need,), torch.uint8, dev)
+        logits = torch.empty((bs, 3, n, 1), dtype=torch.float32, device=dev)
+        fold = torch.empty(_lib.query("smos_point_head_train_fold_floats"), dtype=torch.float32, device=dev)
+        dstat = torch.empty(_lib.query("smos_point_head_train_stat_doubles"), dtype=torch.float64, device=dev)
+        rm1, rv1, rm2, rv2 = buffers
+        params = (w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, w3, bias3)
+        pitch = _lib.i64_array([_point_head_pitch(t) for t in (a, b, c)])
+        with _on(dev), profiling.span_f("point_head_%s[%dx%d]", ("train" if training else "eval", bs, n)):
+            _lib.call("smos_point_head_train_fwd", a.data_ptr(), b.data_ptr(), c.data_ptr(), pitch, _ptr(masks), scale, bs, n,
+                      int(training), _point_mlp_ptrs(params), _lib.f64_array(eps_mom), logits.data_ptr(), fold.data_ptr(),
+                      dstat.data_ptr(), work.data_ptr(), need, _stream(a))
+        ctx.save_for_backward(a, b, c, fold, masks)
+        ctx.param_like = (w1, g1, b1, w2, g2, b2, w3, bias3)
+        ctx.scale, ctx.training = scale, bool(training)
+        return logits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_logits):
+        a, b, c, fold, masks = ctx.saved_tensors
+        bs, _, n = a.shape[:3]
+        dev = a.device
+        gl = grad_logits.to(torch.float32).contiguous()
+        want_x = any(ctx.needs_input_grad[:3])
+        dx = [torch.empty((bs, 64, n, 1), dtype=torch.float32, device=dev) for _ in range(3)] if want_x else [None] * 3
+        dp = [torch.empty_like(p) if ctx.needs_input_grad[3 + i] else None for i, p in enumerate(ctx.param_like)]
+        if want_x or any(g is not None for g in dp):
+            need = _lib.query("smos_point_head_train_work_bytes", bs * n)
+            work = _stream_workspace("point_head_train", (need,), torch.uint8, dev)
+            pitch = _lib.i64_array([_point_head_pitch(t) for t in (a, b, c)])
+            with _on(dev), profiling.span_f("point_head_bwd[%dx%d]", (bs, n)):
+                _lib.call("smos_point_head_train_bwd", a.data_ptr(), b.data_ptr(), c.data_ptr(), pitch, _ptr(masks), ctx.scale,
+                          gl.data_ptr(), bs, n, int(ctx.training), fold.data_ptr(), _point_mlp_ptrs(dx + dp), work.data_ptr(),
+                          need, _stream(a))
+        dx = [g if ctx.needs_input_grad[i] else None for i, g in enumerate(dx)]
+        return (*dx, *dp, None, None, None, None, None)
+
+
+def _point_head_conv(name, m, shape, bias):
+    if not isinstance(m, torch.nn.Module):
+        raise RuntimeError("point_head_train: %s must be the convolution module" % name)
+    if (m.bias is not None) != bias:
+        raise RuntimeError("point_head_train: %s %s a bias; conv1 and conv2 have none, conv3 has one"
+                           % (name, "lacks" if bias else "has"))
+    w = m.weight
+    if tuple(w.shape[:2]) != shape or w.numel() != shape[0] * shape[1]:
+        raise RuntimeError("point_head_train: %s is %s, want a 1x1 convolution %d -> %d" % (name, tuple(w.shape), shape[1], shape[0]))
+    return w
+
+
+def point_head_train(a, b, c, conv1, bn1, conv2, bn2, conv3, p=0.2, training=None, keep=None):
+    """``PredBranch(CatFusion(a, b, c))`` -- cat -> dropout p -> 1x1 192->96 -> BN -> ReLU -> 1x1 96->64 -> BN -> ReLU ->
+    dropout p -> 1x1 64->3 + bias -- as one autograd op on the HIP kernels of csrc/point_head_train.hip.
+
+    a, b, c [B,64,N,1] float32 on the GPU, dense or cut out of a longer point axis; conv1/conv2 the bias-free 1x1
+    convolutions, conv3 the one with a bias, bn1/bn2 the batch norms (affine, with running statistics and a momentum).
+    ``training`` (None: ``bn1.training``): batch statistics over all B*N points, the four running buffers and
+    ``num_batches_tracked`` updated in place as the modules would, and both dropouts applied; otherwise the running
+    statistics and no dropout.  ``p`` is 0.2 (the kernels' keep threshold) or 0.0 (no dropout).  ``keep = (keep1 [B,192,N]
+    bool, keep2 [B,64,N] bool)`` gives the dropout masks; without it they are drawn on the device from two seed words taken
+    from torch's generator of that device, so ``torch.manual_seed`` reproduces them (against themselves, not against
+    torch's dropout stream).  ``point_head_keep_bits(result)`` returns the masks a call used.  Returns logits [B,3,N,1],
+    differentiable in the inputs and the eight parameters; a gradient nobody needs is not computed.  Every sum runs in a
+    fixed order (the bits do not depend on the grid or the run) and nothing is read back to the host."""
+    _require_cuda("point_head_train", a, b, c)
+    xs = [a, b, c]
+    for i, x in enumerate(xs):
+        if x.dtype != torch.float32:
+            raise RuntimeError("point_head_train: float32 only (input %d is %s)" % (i, x.dtype))
+        if x.dim() == 3:
+            xs[i] = x = x[..., None]
+        if x.dim() != 4 or x.shape[1] != 64 or x.shape[3] != 1 or x.shape != xs[0].shape or x.shape[0] * x.shape[2] == 0:
+            raise RuntimeError("point_head_train: input %d is %s, want three equal [B,64,N(,1)] with B*N > 0" % (i, tuple(x.shape)))
+        if x.device != xs[0].device:
+            raise RuntimeError("point_head_train: inputs on %s and %s" % (xs[0].device, x.device))
+        if _point_head_pitch(x) is None:
+            raise RuntimeError("point_head_train: input %d has strides %s; want unit-strided points and equally spaced channels "
+                               "(make it contiguous)" % (i, x.stride()))
+    bs, _, n = xs[0].shape[:3]
+    dev = xs[0].device
+    training = bool(bn1.training if training is None else training)
+    for i, (bn, ch) in enumerate(((bn1, 96), (bn2, 64)), 1):
+        if bn.weight is None or bn.bias is None or bn.running_mean is None or bn.running_var is None or bn.momentum is None:
+            raise RuntimeError("point_head_train: bn%d must be affine, track running statistics and have a momentum" % i)
+        if bn.weight.numel() != ch:
+            raise RuntimeError("point_head_train: bn%d has %d channels, want %d" % (i, bn.weight.numel(), ch))
+    w1 = _point_head_conv("conv1", conv1, (96, 192), False)
+    w2 = _point_head_conv("conv2", conv2, (64, 96), False)
+    w3 = _point_head_conv("conv3", conv3, (3, 64), True)
+    tensors = [w1, bn1.weight, bn1.bias, w2, bn2.weight, bn2.bias, w3, conv3.bias]
+    buffers = (bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var)
+    for t in tensors + list(buffers):
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("point_head_train: parameters and buffers must be contiguous float32 tensors on %s" % dev)
+    if _lib.query("smos_point_head_train_work_bytes", bs * n) <= 0:
+        raise RuntimeError("point_head_train: %d x %d points is more than the kernels are set up for" % (bs, n))
+    if training and bs * n < 2:
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (torch.Size((bs, 96, n, 1)),))
+    p = float(p)
+    if p not in (0.0, 0.2):
+        raise RuntimeError("point_head_train: p = %g; the kernels keep with probability 0.8 (p = 0.2) or everything (p = 0)" % p)
+    masks = seed = None
+    if training and p > 0.0:
+        masks = torch.empty(_lib.query("smos_point_head_train_mask_words", bs * n), dtype=torch.int32, device=dev)
+        k1 = k2 = None
+        if keep is not None:
+            k1, k2 = keep
+            for k, ch in ((k1, 192), (k2, 64)):
+                if k.dtype != torch.bool or k.device != dev or tuple(k.shape[:3]) != (bs, ch, n) or k.numel() != bs * ch * n:
+                    raise RuntimeError("point_head_train: keep must be bool (keep1 [B,192,N], keep2 [B,64,N]) on %s" % dev)
+            k1, k2 = k1.contiguous(), k2.contiguous()
+        else:
+            seed = torch.randint(-2 ** 63, 2 ** 63 - 1, (2,), dtype=torch.int64, device=dev)
+        with _on(dev), profiling.span_f("point_head_masks[%dx%d]", (bs, n)):
+            _lib.call("smos_point_head_train_masks", _ptr(k1), _ptr(k2), _ptr(seed), bs, n, masks.data_ptr(), _stream(xs[0]))
+    elif keep is not None and training:
+        raise RuntimeError("point_head_train: keep masks given with p = 0")
+    eps_mom = (float(bn1.eps), float(bn2.eps), float(bn1.momentum), float(bn2.momentum))
+    need_grad = torch.is_grad_enabled()
+    xin = [x if need_grad and x.requires_grad else x.detach() for x in xs]
+    out = _PointHeadTrain.apply(*xin, *tensors, buffers, eps_mom, training, masks, 1.0 / (1.0 - p))
+    if training:
+        for bn in (bn1, bn2):
+            if bn.num_batches_tracked is not None:
+                bn.num_batches_tracked.add_(1)
+    out._smos_point_head = (masks, seed, bs, n)
+    return out
+
+
+def point_head_keep_bits(out):
+    """(keep1 [B,192,N] bool, keep2 [B,64,N] bool) of the ``point_head_train`` call that returned ``out``, unpacked from the
+    packed words its kernels read; None when that call dropped nothing (eval, or p = 0)."""
+    masks, _, bs, n = out._smos_point_head
+    if masks is None:
+        return None
+    words = masks.view(8, bs, n)                                   # word planes: [w][b][n]
+    shifts = torch.arange(32, device=masks.device, dtype=torch.int32)
+    bits = ((words[:, None] >> shifts[None, :, None, None]) & 1).bool()      # [w][bit][b][n]
+    bits = bits.reshape(256, bs, n).permute(1, 0, 2)               # channel = 32 w + bit
+    return bits[:, :192].contiguous(), bits[:, 192:].contiguous()
+
+
 def msda_fwd(value, spatial_shapes, level_start_index, sampling_loc, attn_weight):
     """value [N,S,M,D], shapes [L,2] int64 (device), level_start [L] int64 (device), loc [N,Lq,M,L,P,2],
     attn [N,Lq,M,L,P] -> [N,Lq,M*D]."""

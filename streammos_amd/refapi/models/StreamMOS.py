@@ -114,8 +114,7 @@ class AttNet(nn.Module):
         point_bev = self.bev_grid2point(bev_feat, cur_xy)
 
         pts_cur = pts.view(bs, t, -1, n, 1)[:, 0].contiguous()
-        fused = self.point_post(pts_cur, point_bev, point_feat_1)
-        pred_cls = self.pred_layer(fused).float()
+        pred_cls = backbone.point_head(self.point_post, self.pred_layer, pts_cur, point_bev, point_feat_1).float()
         return pred_cls, aux0, aux1, aux2, memory
 
     def infer(self, batch, i, query_embed_store=None):

@@ -21,7 +21,7 @@ class Refine(nn.Module):
         self.bf_pred_layer = backbone.PredBranch(point_feat_out_channels, class_num)
 
     def forward(self, point_feat_tmp_cur, point_bev_feat, point_feat_1):
-        return self.bf_pred_layer(self.bf_point_post(point_feat_tmp_cur, point_bev_feat, point_feat_1)).float()
+        return backbone.point_head(self.bf_point_post, self.bf_pred_layer, point_feat_tmp_cur, point_bev_feat, point_feat_1).float()
 
 
 class AttNet(_base.AttNet):

@@ -169,6 +169,61 @@ class CatFusion(nn.Module):
         return self.merge_layer(x)
 
 
+def _point_head_modules(fusion, pred, xs):
+    """(conv1, bn1, conv2, bn2, conv3) where ops.point_head_train computes ``pred(fusion(*xs))``, else None: the switch is on
+    (ops.point_head_fused, SMOS_POINT_HEAD_TRAIN, default 0), xs are three CUDA float32 [B,64,N,1] the kernels can read in
+    place, no autocast, the modules are exactly 192 -> 96 -> 64 -> 3 with the expected types, the batch norms are
+    single-process, fusion and pred are in the same mode, and either they train or gradients are enabled and an input or
+    a parameter needs one.  Everything else stays on the modules."""
+    if not ops.point_head_fused():
+        return None
+    if type(fusion) is not CatFusion or type(pred) is not PredBranch or len(xs) != 3 or fusion.training != pred.training:
+        return None
+    for x in xs:
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape == xs[0].shape
+                and x.device == xs[0].device and x.shape[1] == 64 and x.shape[3] == 1 and x.shape[0] * x.shape[2] > 0
+                and ops._point_head_pitch(x) is not None):
+            return None
+    if torch.is_autocast_enabled():
+        return None
+    merge, head = list(fusion.merge_layer), list(pred.pred_layer)
+    if len(merge) != 6 or len(head) != 1 or not all(type(m) is nn.ReLU for m in (merge[2], merge[5])):
+        return None
+    conv1, bn1, conv2, bn2, conv3 = merge[0], merge[1], merge[3], merge[4], head[0]
+    dev = xs[0].device
+    for conv, cin, cout, bias in ((conv1, 192, 96, False), (conv2, 96, 64, False), (conv3, 64, 3, True)):
+        if not (type(conv) is nn.Conv2d and conv.in_channels == cin and conv.out_channels == cout
+                and (conv.bias is not None) == bias and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+                and conv.padding == (0, 0) and conv.groups == 1 and conv.weight.dtype == torch.float32
+                and conv.weight.device == dev):
+            return None
+    for bn, c in ((bn1, 96), (bn2, 64)):
+        if type(bn) is nn.SyncBatchNorm:
+            dist = torch.distributed
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size(bn.process_group) > 1:
+                return None
+        elif type(bn) is not nn.BatchNorm2d:
+            return None
+        if not (bn.num_features == c and bn.affine and bn.track_running_stats and bn.momentum is not None
+                and bn.running_mean is not None and bn.training == fusion.training
+                and bn.weight.dtype == torch.float32 and bn.weight.device == dev):
+            return None
+    if not fusion.training:
+        params = [conv1.weight, bn1.weight, bn1.bias, conv2.weight, bn2.weight, bn2.bias, conv3.weight, conv3.bias]
+        if not (torch.is_grad_enabled() and any(t.requires_grad for t in list(xs) + params)):
+            return None
+    return conv1, bn1, conv2, bn2, conv3
+
+
+def point_head(fusion, pred, *xs):
+    """``pred(fusion(*xs))``, the point head of AttNet.stage_forward and of Refine.forward: through ops.point_head_train
+    where ``_point_head_modules`` allows it, else through the two modules as they are."""
+    fused = _point_head_modules(fusion, pred, xs)
+    if fused is not None:
+        return ops.point_head_train(*xs, *fused, p=0.2, training=fusion.training)
+    return pred(fusion(*xs))
+
+
 _OWN_BACKWARD = os.environ.get("SMOS_BILINEAR_BWD", "1") != "0"    # A/B switch: 0 = training through F.grid_sample
 
 
