@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMOS_ABI_VERSION 2
+#define SMOS_ABI_VERSION 3
 
 enum smos_status {
   SMOS_OK = 0,
@@ -453,6 +453,21 @@ int smos_upconv_xpass(const float* z, float* t, int64_t B, int64_t Hs, int64_t W
 int smos_upconv_ypass(const float* conv_a, int64_t a_pitch, const float* bias, const float* t1, int64_t H1, const float* t2,
                       int64_t H2, float* out, int64_t out_pitch, int64_t B, int64_t Ho, int64_t Wo, int64_t C, int32_t act,
                       smos_stream_t stream);
+/* The adjoint of the two passes (csrc/upconv_bwd.hip; the backward of ops.upconv3x3_train): from the output gradient
+ * g [B, Ho, Wo, *] (row pitch g_pitch >= C) the gradient of one source's tap products,
+ *     gz[b, ys, xs, (3 ky + kx) C + c] = sum_{Y, X} wy(Y + ky - 1 -> ys) wx(X + kx - 1 -> xs) g[b, Y, X, c]
+ * with the float32 weights the forward applies and the taps that leave the Ho x Wo image dropped, in two launches:
+ *   smos_upconv_bwd_ypass  s [B, 3, Hs, Wo, C] <- sum over the fine rows D that read source row ys of wy * g[b, D - ky + 1, X, c]
+ *   smos_upconv_bwd_xpass  gz [B * Hs * Ws, *] (row pitch gz_pitch >= 9 * C; the layout of z) <- sum over the fine columns D
+ *                          that read source column xs of wx * s[b, ky, ys, D - kx + 1, c]
+ * Gather form: every element is summed by one thread in ascending D over smos_upconv_bwd_window(n_src, n_dst) candidates --
+ * no atomics, the same bits on every run and for every grid.  max_blocks caps the grid (0: no cap; fewer blocks walk
+ * the same elements in several trips).  The element-count limits of the forward passes, and n_src * n_dst <= 2^22 per axis. */
+int smos_upconv_bwd_window(int64_t n_src, int64_t n_dst);
+int smos_upconv_bwd_ypass(const float* g, int64_t g_pitch, float* s, int64_t B, int64_t Ho, int64_t Wo, int64_t C, int64_t Hs,
+                          int64_t max_blocks, smos_stream_t stream);
+int smos_upconv_bwd_xpass(const float* s, float* gz, int64_t gz_pitch, int64_t B, int64_t Hs, int64_t Ws, int64_t C, int64_t Wo,
+                          int64_t max_blocks, smos_stream_t stream);
 
 /* CatFusion + PredBranch (networks/backbone.py:387-413, 188-196): rows [B*N, K1] (row pitch in floats) ->
  * 1x1 K1->M1 + ReLU -> 1x1 M1->M2 + ReLU -> 1x1 M2->M3 + bias, out [B, M3, N]; one kernel, intermediates in registers

@@ -81,6 +81,9 @@ SIGNATURES = {
     "smos_upconv_xy_ok": [i64, i64],
     "smos_upconv_xy": [vp, i64, vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i64, i64, i32, vp],
     "smos_upconv_xy_units": [vp, i64, vp, vp, i64, i64, vp, i64, i64, vp, i64, i64, i64, i64, i64, i32, i32, i64, vp],
+    "smos_upconv_bwd_window": [i64, i64],
+    "smos_upconv_bwd_ypass": [vp, i64, vp, i64, i64, i64, i64, i64, i64, vp],
+    "smos_upconv_bwd_xpass": [vp, vp, i64, i64, i64, i64, i64, i64, i64, vp],
     "smos_prep_transform_mask": [vp, i64, c_f64p, c_f64p, vp, vp, vp],
     "smos_prep_emit": [vp, vp, vp, i64, i32, i32, i64, i32, c_f32p, c_f32p, c_f64p, c_i64p, c_f64p, vp, vp, vp, vp],
     "smos_prep_unpad_labels": [vp, i64, vp, vp, i64, vp, vp],
@@ -130,7 +133,7 @@ INT64_RESULTS = (
     "smos_point_head_train_work_bytes", "smos_point_head_train_mask_words",
 )
 
-ABI_VERSION = 2      # SMOS_ABI_VERSION of the include/smos.h these signatures were written against
+ABI_VERSION = 3      # SMOS_ABI_VERSION of the include/smos.h these signatures were written against
 
 _lib = None
 

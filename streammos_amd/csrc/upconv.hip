@@ -14,35 +14,16 @@
 // in float32 it differs from the direct form by summation order only.  conv_1 falls from 48.3 to 15.7 GFLOP per sample
 // and the 320-channel concatenated input (336 MB) is never built.
 // Interpolation weights: ATen's align_corners=True formula, as in upsample_concat_cl (cl_kernels.hip).
+// The adjoint of the two passes, for the training backward (ops.upconv3x3_train), is csrc/upconv_bwd.hip.
 #include "smos_common.h"
+#include "upconv_lerp.h"      // Lerp, lerp_of, lerp_add: shared with the adjoint (csrc/upconv_bwd.hip)
 
 namespace smos {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-struct Lerp {
-  int i0, step;     // source index and 0/1 step to the second tap
-  float w0, w1;
-};
-
-__device__ __forceinline__ Lerp lerp_of(int dst, int n_src, int n_dst) {
-  const float r = n_dst > 1 ? (float)(n_src - 1) / (float)(n_dst - 1) : 0.0f;
-  const float s = r * dst;
-  Lerp l;
-  l.i0 = (int)s;
-  l.step = (l.i0 < n_src - 1) ? 1 : 0;
-  l.w1 = s - l.i0;
-  l.w0 = 1.0f - l.w1;
-  return l;
-}
-
 // The statements both forms share, so that -ffp-contract=on forms the same FMAs in the pair and in the one launch:
-// one bilinear tap pair added to four channels, and the epilogue.
-__device__ __forceinline__ void lerp_add(float4& acc, float w0, float w1, const float4& a0, const float4& a1) {
-  acc.x += w0 * a0.x + w1 * a1.x; acc.y += w0 * a0.y + w1 * a1.y;
-  acc.z += w0 * a0.z + w1 * a1.z; acc.w += w0 * a0.w + w1 * a1.w;
-}
-
+// one bilinear tap pair added to four channels (lerp_add, upconv_lerp.h), and the epilogue.
 __device__ __forceinline__ float4 bias_act(const float4& acc, const float4& bv, int act) {   // act: 0 none, 1 ReLU, 2 LeakyReLU(0.01)
   float4 o = make_float4(acc.x + bv.x, acc.y + bv.y, acc.z + bv.z, acc.w + bv.w);
   if (act == 1) {

@@ -1859,6 +1859,161 @@ def upconv_xy_units(conv_a, bias, z1, z2, act, strip, max_blocks=0, out=None):
     return out
 
 
+_conv1_fused = None
+
+
+def set_conv1_fused(flag):
+    """Explicit setting of ``conv1_fused`` (True / False), or None to hand the decision back to the environment.
+    Returns the previous explicit setting."""
+    global _conv1_fused
+    prev, _conv1_fused = _conv1_fused, (None if flag is None else bool(flag))
+    return prev
+
+
+def conv1_fused():
+    """Whether ``CENet_Transformer.forward`` (refapi/networks/multi_view_encoder.py) may run the decoder's conv_1 on
+    ``upconv3x3_train``: the ``set_conv1_fused`` setting if there is one, else ``SMOS_CONV1_TRAIN`` in the environment
+    (default 0), read per call."""
+    if _conv1_fused is not None:
+        return _conv1_fused
+    return os.environ.get("SMOS_CONV1_TRAIN", "0").strip().lower() not in ("", "0", "false", "off", "no")
+
+
+# the layout upconv3x3_train returns: "cl" the channels-last-strided map its kernels write, "nchw" a contiguous copy of it
+# (a development knob for that one A/B, read once at import -- unlike the switch above, which is read per call; DESIGN.md
+# 4.9b has the measurement behind the default)
+_CONV1_OUT = os.environ.get("SMOS_CONV1_OUT", "cl")
+
+
+def _as_cl(t, dense=False):
+    """t [B,C,H,W] as a channels-last view the kernels can read (``_cl``; dense: rows of exactly C floats): t itself where
+    its strides already say so, else a channels-last copy."""
+    b, c, h, w = t.shape
+    s0, s1, s2, pitch = t.stride()
+    if s1 == 1 and s2 == w * pitch and (b == 1 or s0 == h * w * pitch) and (pitch == c if dense else pitch >= c) and pitch % 4 == 0 \
+            and t.data_ptr() % 16 == 0:
+        return t
+    out = empty_cl(b, c, h, w, t.device)
+    out.copy_(t)
+    return out
+
+
+def upconv_adjoint(g, hs, ws, max_blocks=0, out=None, scratch=None):
+    """The adjoint of upconv3x3's two passes for one source of Hs x Ws pixels (csrc/upconv_bwd.hip): g, the gradient of the
+    output as a channels-last [B,C,Ho,Wo] view, -> G [B*Hs*Ws, 9*C], the gradient of that source's tap products, in the
+    layout of the forward's z.  Two launches (y adjoint into ``scratch`` [B,3,Hs,Wo,C], x adjoint into ``out``), each element
+    summed by one thread in a fixed order: the same bits on every run and for every ``max_blocks`` (a cap on both grids, 0:
+    none).  out: a float32 [B*Hs*Ws, 9*C] view with contiguous channels (e.g. a column range of a wider matrix)."""
+    _require_cuda("upconv_adjoint", g, out, scratch)
+    if g.dim() != 4 or g.dtype != torch.float32:
+        raise RuntimeError("upconv_adjoint: g must be a float32 [B,C,Ho,Wo] map, got %s %s" % (tuple(g.shape), g.dtype))
+    b, c, ho, wo = g.shape
+    hs, ws = int(hs), int(ws)
+    gp = _cl("upconv_adjoint", g)
+    if scratch is None:
+        scratch = torch.empty((b, 3, hs, wo, c), dtype=torch.float32, device=g.device)
+    elif scratch.dtype != torch.float32 or scratch.numel() != b * 3 * hs * wo * c or not scratch.is_contiguous():
+        raise RuntimeError("upconv_adjoint: scratch must be a contiguous float32 [B,3,Hs,Wo,C] tensor")
+    if out is None:
+        out = torch.empty((b * hs * ws, 9 * c), dtype=torch.float32, device=g.device)
+    elif out.dim() != 2 or tuple(out.shape) != (b * hs * ws, 9 * c) or out.stride(1) != 1 or out.dtype != torch.float32:
+        raise RuntimeError("upconv_adjoint: out must be a float32 [B*Hs*Ws, 9*C] view with contiguous channels")
+    zp = out.stride(0) if out.shape[0] > 1 else max(out.stride(0), 9 * c)
+    with _on(g.device):
+        st = _stream(g)
+        with profiling.span_f("upconv_bwd_ypass[%dx%dx%dx%d->%d]", (b, ho, wo, c, hs)):
+            _lib.call("smos_upconv_bwd_ypass", g.data_ptr(), gp, scratch.data_ptr(), b, ho, wo, c, hs, int(max_blocks), st)
+        with profiling.span_f("upconv_bwd_xpass[%dx%dx%dx%d<-%d]", (b, hs, ws, c, wo)):
+            _lib.call("smos_upconv_bwd_xpass", scratch.data_ptr(), out.data_ptr(), zp, b, hs, ws, c, wo, int(max_blocks), st)
+    return out
+
+
+def _upconv_dx(gz, w, shape):
+    """dX = G nk: the data gradient of one source, [B,128,Hs,Ws] (channels-last strides), from G [P, 9*C] and w [C,128,3,3]."""
+    b, cin, hs, ws = shape
+    nk = w.permute(2, 3, 0, 1).reshape(-1, cin).float()           # [9*C, Cin], tap-major: TapWeights.nk
+    return torch.mm(gz, nk).view(b, hs, ws, cin).permute(0, 3, 1, 2)
+
+
+def _upconv_dw(gz, x):
+    """dW from dNK = G^T X: the weight gradient of one source, [C,128,3,3], from G [P, 9*C] and x [B,128,Hs,Ws]."""
+    cin = x.shape[1]
+    rows = _as_cl(x, dense=True).permute(0, 2, 3, 1).reshape(-1, cin)
+    return torch.mm(gz.t(), rows).view(3, 3, -1, cin).permute(2, 3, 0, 1)
+
+
+class _Upconv3x3Train(torch.autograd.Function):
+    """ops.upconv3x3_train.  Kept for the backward: the sources and their weights as they came in -- no activation, no tap
+    product, no resized map."""
+
+    @staticmethod
+    def forward(ctx, conv_a, *xw):
+        b, c, ho, wo = conv_a.shape
+        a = _as_cl(conv_a)
+        out = a if a is not conv_a else empty_cl(b, c, ho, wo, conv_a.device)      # a fresh copy is finished in place
+        srcs = [(_as_cl(xw[i], dense=True), TapWeights(xw[i + 1], 0, xw[i + 1].shape[1])) for i in range(0, len(xw), 2)]
+        upconv3x3(a, torch.zeros(c, dtype=torch.float32, device=conv_a.device), srcs, 0, out=out)
+        ctx.save_for_backward(*xw)
+        return out.contiguous() if _CONV1_OUT == "nchw" else out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        xw = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grads = [g if need[0] else None]
+        gcl = None
+        for i in range(0, len(xw), 2):
+            x, w = xw[i], xw[i + 1]
+            dx = dw = None
+            if need[1 + i] or need[2 + i]:
+                if gcl is None:
+                    gcl = _as_cl(g.float())
+                gz = upconv_adjoint(gcl, x.shape[2], x.shape[3])
+                if need[1 + i]:
+                    dx = _upconv_dx(gz, w, x.shape)
+                if need[2 + i]:
+                    dw = _upconv_dw(gz, x)
+            grads += [dx, dw]
+        return tuple(grads)
+
+
+def upconv3x3_train(conv_a, sources):
+    """``conv_a + sum over sources of conv3x3(bilinear_up(x_src, align_corners=True), w_src, padding 1)`` as one autograd op
+    that never builds the resized maps: the training form of ``upconv3x3``.
+
+    conv_a [B,C,Ho,Wo]: the ordinary convolution of the channels that are not upsampled, computed by the caller; sources: one
+    or two (x_src [B,128,Hs,Ws], w_src [C,128,3,3]); float32 on the GPU, any strides (what is not a channels-last view is
+    copied into one).  No bias and no activation.  The forward IS ``upconv3x3`` (tap products at source resolution, then the
+    interpolation launch), with the tap weights rebuilt from w_src on the device at every call.  The backward returns the
+    output gradient itself for conv_a and, per source, runs the adjoint of the interpolation in HIP (``upconv_adjoint``)
+    followed by two library matrix products at source resolution, dX = G nk and dW from G^T X; a gradient nobody needs is
+    not computed.  Returns a logical [B,C,Ho,Wo] tensor with channels-last strides."""
+    _require_cuda("upconv3x3_train", conv_a)
+    if conv_a.dim() != 4 or conv_a.dtype != torch.float32 or conv_a.numel() == 0:
+        raise RuntimeError("upconv3x3_train: conv_a must be a non-empty float32 [B,C,Ho,Wo] map, got %s %s" % (tuple(conv_a.shape), conv_a.dtype))
+    b, c = conv_a.shape[:2]
+    if c % 4 or 9 * c > 2048:
+        raise RuntimeError("upconv3x3_train: %d output channels; the tap-product kernels take multiples of 4 up to 224" % c)
+    sources = list(sources)
+    if not 1 <= len(sources) <= 2:
+        raise RuntimeError("upconv3x3_train: one or two upsampled sources, got %d" % len(sources))
+    flat = []
+    for i, src in enumerate(sources):
+        if len(src) != 2:
+            raise RuntimeError("upconv3x3_train: source %d must be (x_src, w_src)" % i)
+        x, w = src
+        _require_cuda("upconv3x3_train", x, w)
+        if x.dim() != 4 or x.dtype != torch.float32 or x.shape[0] != b or x.shape[1] != 128 or x.numel() == 0:
+            raise RuntimeError("upconv3x3_train: source %d is %s %s, want float32 [%d,128,Hs,Ws]" % (i, tuple(x.shape), x.dtype, b))
+        if tuple(w.shape) != (c, 128, 3, 3) or w.dtype != torch.float32:
+            raise RuntimeError("upconv3x3_train: weights of source %d are %s %s, want float32 [%d,128,3,3]" % (i, tuple(w.shape), w.dtype, c))
+        if x.device != conv_a.device or w.device != conv_a.device:
+            raise RuntimeError("upconv3x3_train: source %d on %s / %s, conv_a on %s" % (i, x.device, w.device, conv_a.device))
+        flat += [x, w]
+    return _Upconv3x3Train.apply(conv_a, *flat)
+
+
 STEM_TAPS = (1, 2, 2, 4)      # 3x3 taps that reach an output pixel under stride 2, per parity class (y&1)*2 + (x&1)
 
 

@@ -13,6 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import backbone
+from ... import ops
 from .. import deep_point
 from ..deformattn.modules import MSDeformAttn
 
@@ -187,6 +188,27 @@ class CENet_Transformer(nn.Module):
         back = VoxelMaxPool(pcds_feat=pts, pcds_ind=bev_xy, output_size=bev_size, scale_rate=scale)
         return torch.cat((bev, back), dim=1), pts
 
+    def _conv1_fused(self, x0, x1, x2):
+        """Whether forward runs conv_1 on ops.upconv3x3_train: the switch is on (ops.conv1_fused, SMOS_CONV1_TRAIN, default 0),
+        the three maps are CUDA float32 with 64 / 128 / 128 channels, no autocast, the module trains or gradients are enabled,
+        and conv_1 is exactly the BasicConv2d 320 -> 128, 3x3, stride 1, padding 1, no bias (with the auxiliary heads in
+        place).  Everything else stays on the modules."""
+        if not ops.conv1_fused() or not self.aux:
+            return False
+        for t, c in ((x0, 64), (x1, 128), (x2, 128)):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[1] == c
+                    and t.device == x0.device and t.shape[0] == x0.shape[0] and t.numel() > 0):
+                return False
+        if torch.is_autocast_enabled() or not (self.training or torch.is_grad_enabled()):
+            return False
+        m = self.conv_1
+        if type(m) is not BasicConv2d or type(m.conv) is not nn.Conv2d or type(m.relu) is not nn.LeakyReLU:
+            return False
+        conv = m.conv
+        return (conv.in_channels == 320 and conv.out_channels == 128 and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
+                and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
+                and conv.padding_mode == "zeros" and conv.weight.dtype == torch.float32 and conv.weight.device == x0.device)
+
     def forward(self, x, pcds_cood_cur, pcds_sphere_coord_cur, query_embed_store, use_query_store=False,
                 return_query=False):
         x0 = self.header_bev(x)
@@ -211,10 +233,21 @@ class CENet_Transformer(nn.Module):
         x2 = fused.transpose(2, 1).reshape(bs, c, hh, ww)
 
         size = x0.shape[2:]
-        res = [F.interpolate(t, size=size, mode="bilinear", align_corners=True) for t in (x0, x1, x2)]
-        out = self.conv_2(self.conv_1(torch.cat(res, dim=1)))
-        if self.aux:
-            res = [self.aux_head1(res[0]), self.aux_head2(res[1]), self.aux_head3(res[2])]
+        if self._conv1_fused(x0, x1, x2):
+            # conv_1 without the resized maps and their concatenation (ops.upconv3x3_train): the x0 part stays
+            # an ordinary convolution, the x1 and x2 parts are taken at their own resolution.  The auxiliary heads are 1x1
+            # convolutions with a bias: they commute with the interpolation (its weights sum to 1), so their three-channel
+            # logits are resized instead of their 128-channel inputs
+            w = self.conv_1.conv.weight
+            y = ops.upconv3x3_train(F.conv2d(x0, w[:, :64], padding=1), [(x1, w[:, 64:192]), (x2, w[:, 192:320])])
+            out = self.conv_2(self.conv_1.relu(self.conv_1.bn(y)))
+            res = [self.aux_head1(x0)] + [F.interpolate(head(t), size=size, mode="bilinear", align_corners=True)
+                                          for head, t in ((self.aux_head2, x1), (self.aux_head3, x2))]
+        else:
+            res = [F.interpolate(t, size=size, mode="bilinear", align_corners=True) for t in (x0, x1, x2)]
+            out = self.conv_2(self.conv_1(torch.cat(res, dim=1)))
+            if self.aux:
+                res = [self.aux_head1(res[0]), self.aux_head2(res[1]), self.aux_head3(res[2])]
         if return_query:
             return out, x1_point, res[0], res[1], res[2], x2
         return out, res[0], res[1], res[2]
