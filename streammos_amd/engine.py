@@ -20,14 +20,16 @@ tensors; on a GPU in eval mode they hand over to this engine, which computes the
 The engine holds *copies* of the folded weights: it is rebuilt whenever the module's parameters may have
 changed (``load_state_dict``, ``.to()``, ``.train()``), see ``AttNet._engine_for``.
 """
+import itertools
 import os
 
 import torch
 import torch.nn.functional as F
 
-from . import ops, profiling
+from . import ops, profiling, scratch
 
 RELU, LEAKY, NONE = ops.ACT_RELU, ops.ACT_LEAKY, ops.ACT_NONE
+_gated_tags = itertools.count()         # BasicBlock.tag: a small integer per gated block built
 
 
 def _fold(conv_w, conv_b, bn, pre=None):
@@ -117,7 +119,7 @@ class UnbalanceBlock:
 class BasicBlock:
     """BasicBlock (networks/backbone.py:136-159): conv3x3 + BN + ReLU, conv3x3 + BN [, ChannelAtt gate], + x, ReLU."""
     kind = "basic"
-    __slots__ = ("w1", "b1", "w2", "b2", "att", "cw1", "cb1", "cw2", "cb2", "plan_ok", "plan", "scratch")
+    __slots__ = ("w1", "b1", "w2", "b2", "att", "cw1", "cb1", "cw2", "cb2", "plan_ok", "plan", "tag")
 
     def __init__(self, m):
         self.w1, self.b1 = _fold(m.layer[0].weight, None, m.layer[1])
@@ -133,7 +135,7 @@ class BasicBlock:
         c = self.w1.shape[0]
         self.plan_ok = tuple(self.w1.shape) == (c, c, 3, 3) and tuple(self.w2.shape) == (c, c, 3, 3) and ops.basic_block_ok(c, self.att)
         self.plan = None                # ops.BasicBlockPlan, made by the first block call (a bf16 engine makes none)
-        self.scratch = None             # gated blocks: {(stream, namespace): plane sums}, see InferenceEngine._block_ws
+        self.tag = next(_gated_tags) if m.use_att else None        # gated blocks: names the plane sums in the engine's scratch table
 
     def run(self, eng, x, out=None):
         # a gated block call takes its pool sums from the conv epilogue: without fused_gate_sums it goes launch by launch
@@ -191,7 +193,7 @@ class FusionLayer:
 
 CONV_PRECISIONS = ("fp32", "bf16")
 
-# The A/B switches: (attribute, environment variable, default, kind); kind "bool" parses as != "0", "int" as int().  Each is a
+# The A/B switches: (attribute, environment variable, default, kind); kind "bool" parses by ops.env_on, "int" as int().  Each is a
 # plain attribute read on every call, so setting one on a live engine selects the other route from the next call on.
 SWITCHES = (
     ("sparse_stem", "SMOS_SPARSE_STEM", True, "bool"),        # first BEV stage on the occupied cells (AttNet.engine_sparse_stem overrides)
@@ -229,7 +231,8 @@ def read_switches(obj, table):
     """Set every switch of `table` on `obj` from the environment (or its default)."""
     for attr, var, default, kind in table:
         v = os.environ.get(var)
-        setattr(obj, attr, default if v is None else (v != "0" if kind == "bool" else int(v)))
+        v = ops.env_on(v) if kind == "bool" else (None if v is None else int(v))
+        setattr(obj, attr, default if v is None else v)
 
 
 class InferenceEngine:
@@ -248,6 +251,7 @@ class InferenceEngine:
         self.conv_precision = conv_precision
         self._bf16 = conv_precision == "bf16"
         self._conv_layers = {}          # id(folded weight) -> ops.ConvLayer (which holds the weight): see _conv
+        self.scratch = scratch.Table()      # the gated blocks' plane sums: see _block_ws
         self.device = next(net.parameters()).device
         read_switches(self, SWITCHES)
         if self._bf16:
@@ -381,20 +385,12 @@ class InferenceEngine:
         return (pred,) + a3 + (x2,)
 
     def _block_ws(self, p, n_floats):
-        """Scratch of one channel-attention block (plane sums written by one kernel, read by the next).  Keyed by
-        (block, HIP stream, scratch namespace): blocks of different pipeline stages run concurrently on different streams, the same
-        block may run on two streams at once (encode(t) on the main stream next to encode(t+1) on the side stream), and
-        hipGraphs captured from one engine for several TTA groups replay concurrently with the addresses baked in
-        (namespace = group index, ops.set_workspace_namespace in StreamRunner._capture_groups) -- a shared scratch would be a data
-        race in each case."""
-        table = p.scratch
-        if table is None:
-            table = p.scratch = ops.new_block_scratch(self.device)     # registered: release_stream_workspaces purges it
-        key = (ops._raw_stream(ops._dev_index(self.device)), ops._ws_namespace)
-        ws = table.get(key)
-        if ws is None or ws.numel() < n_floats:
-            ws = table[key] = torch.zeros(n_floats, dtype=torch.float32, device=self.device)
-        return ws
+        """Scratch of one channel-attention block (plane sums written by one kernel, read by the next), from this engine's
+        table (scratch.py): blocks of different pipeline stages run concurrently on different streams, the same block may
+        run on two streams at once (encode(t) on the main stream next to encode(t+1) on the side stream), and hipGraphs
+        captured from one engine for several TTA groups replay concurrently with the addresses baked in (a namespace per
+        group, StreamRunner._capture_groups) -- a shared scratch would be a data race in each case."""
+        return self.scratch.get(p.tag, (n_floats,), torch.float32, self.device, zero=True)
 
     @staticmethod
     def _add_norm(a, b, norm, c):

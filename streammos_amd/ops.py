@@ -11,61 +11,54 @@ import numpy as np
 import torch
 
 from . import _lib, profiling
+from .scratch import _NO_GUARD, _dev_index, _on, _raw_stream, _stream, shared       # noqa: F401 (tests and tools use them by these names)
+from .scratch import release as release_stream_workspaces       # noqa: F401 (the public name: StreamRunner.close() calls it)
 
 _DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.float64: 2}
-_flag_ws = {}
-_ws_namespace = 0
 
 
-def set_workspace_namespace(tag):
-    """Per-stream scratch (``_stream_workspace``, ``_flag``) is keyed by (device, HIP stream, namespace).  Work that is
-    captured on ONE stream but replayed concurrently on several (the TTA groups of StreamRunner(graph=True, split=k) all use
-    torch's capture stream) selects a namespace per group while it is being captured, so that the groups' graphs do not
-    share scratch.  Returns the previous namespace."""
-    global _ws_namespace
-    prev, _ws_namespace = _ws_namespace, tag
-    return prev
+def env_on(text):
+    """The one spelling rule of the boolean switches: None (unset) or empty -> None (not set); 0 / false / off / no, whatever
+    the case or surrounding whitespace -> False; anything else -> True."""
+    text = (text or "").strip().lower()
+    return None if text == "" else text not in ("0", "false", "off", "no")
 
 
-# The two private torch._C entry points behind torch.cuda.current_stream(...).cuda_stream / torch.cuda.current_device(),
-# resolved once; a torch build without them gets the public (slower: ~4 us + ~3 us per launch) calls instead.
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-_raw_device = getattr(torch._C, "_cuda_getDevice", None)
-if _raw_stream is None:
-    def _raw_stream(index):
-        return torch.cuda.current_stream(index).cuda_stream
-if _raw_device is None:
-    _raw_device = torch.cuda.current_device
+class Switch:
+    """A process-wide A/B switch, resolved on every call: the explicit ``set`` setting if there is one, else the environment
+    variable if it is set (``env_on``), else ``fallback()`` if there is one, else the default."""
+    __slots__ = ("var", "default", "fallback", "explicit")
+
+    def __init__(self, var, default, fallback=None):
+        self.var, self.default, self.fallback, self.explicit = var, default, fallback, None
+
+    def __call__(self):
+        if self.explicit is not None:
+            return self.explicit
+        on = env_on(os.environ.get(self.var))
+        if on is None:
+            on = bool(self.fallback()) if self.fallback is not None else self.default
+        return on
+
+    def set(self, flag):
+        """True / False, or None to hand the decision back to the environment.  Returns the previous explicit setting."""
+        prev, self.explicit = self.explicit, (None if flag is None else bool(flag))
+        return prev
 
 
-def _dev_index(device):
-    return device.index if device.index is not None else _raw_device()
-
-
-def _stream(t):
-    """raw handle of torch's current HIP stream on t's device (the C call behind torch.cuda.current_stream(...).cuda_stream:
-    the wrapper objects cost ~4 us per launch on the host)."""
-    return _raw_stream(_dev_index(t.device))
-
-
-class _NoGuard:
-    """`with` target for a launch on the device that is already current: nothing to switch, nothing to restore."""
-    __slots__ = ()
-
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NO_GUARD = _NoGuard()
-
-
-def _on(device):
-    """Device guard for a launch: torch.cuda.device(...) only where the tensor's device is not the current one (the usual
-    one-process-per-GPU case never switches; the guard object and its two device queries cost ~3 us per launch)."""
-    return _NO_GUARD if device.index is None or _raw_device() == device.index else torch.cuda.device(device)
+# Whether bilinear_gather_backward and msda_bwd (and so the autograd nodes over them) sum in a fixed order (csrc/segsum.hip)
+# when their ``deterministic`` argument is None; torch's own flag (looked up at call time) speaks where nothing else does.
+is_deterministic = Switch("SMOS_DETERMINISTIC", False, lambda: torch.are_deterministic_algorithms_enabled())
+# Whether PointNetStacker.forward (refapi/networks/backbone.py) may route a supported configuration to point_mlp_train,
+point_mlp_fused = Switch("SMOS_POINT_MLP", False)
+# backbone.point_head a supported CatFusion + PredBranch pair to point_head_train,
+point_head_fused = Switch("SMOS_POINT_HEAD_TRAIN", False)
+# and CENet_Transformer.forward (refapi/networks/multi_view_encoder.py) the decoder's conv_1 to upconv3x3_train.
+conv1_fused = Switch("SMOS_CONV1_TRAIN", False)
+# Whether BilinearSample trains through the own backward kernel (off: an A/B against F.grid_sample).
+bilinear_bwd_own = Switch("SMOS_BILINEAR_BWD", True)
+set_deterministic, set_point_mlp_fused, set_point_head_fused = is_deterministic.set, point_mlp_fused.set, point_head_fused.set
+set_conv1_fused, set_bilinear_bwd_own = conv1_fused.set, bilinear_bwd_own.set
 
 
 def _require_cuda(name, *tensors):
@@ -86,17 +79,6 @@ def _live_ptr(name, n_live):
     if n_live.dtype != torch.int32 or n_live.numel() < 1:
         raise RuntimeError("%s: n_live must be a device int32 tensor" % name)
     return n_live.data_ptr()
-
-
-def _flag(device):
-    """4-byte "saw a negative feature" scratch of the scatter; one per (device, stream) so that launches on different
-    HIP streams never share it."""
-    key = (device, _raw_stream(_dev_index(device)), _ws_namespace)
-    ws = _flag_ws.get(key)
-    if ws is None:
-        ws = torch.zeros(4, dtype=torch.int32, device=device)
-        _flag_ws[key] = ws
-    return ws
 
 
 def _dtype_code(name, t):
@@ -122,10 +104,11 @@ def voxel_maxpool_fwd(feat, ind, out, out_size, scale, voxel_max_idx=None):
     if voxel_max_idx is not None and (voxel_max_idx.dtype != torch.int64 or not voxel_max_idx.is_contiguous()):
         raise RuntimeError("voxel_maxpool_fwd: voxel_max_idx must be contiguous int64")
     label = "voxel_maxpool_fwd[%dx%dx%d->%s]" % (bs, c, n, "x".join(str(int(s)) for s in out_size))
+    flag = shared.get("maxpool_flag", (4,), torch.int32, feat.device, zero=True)    # the scatter's "saw a negative feature" word
     with _on(feat.device), profiling.span(label):
         _lib.call("smos_voxel_maxpool_fwd", feat.data_ptr(), _lib.i64_array(feat.stride()[:3]), ind.data_ptr(), out.data_ptr(),
                   _lib.i64_array(out.stride()), _ptr(voxel_max_idx), bs, c, n, d, _lib.i64_array(out_size), _lib.f32_array(scale),
-                  _dtype_code("voxel_maxpool_fwd", feat), _flag(feat.device).data_ptr(), _stream(feat))
+                  _dtype_code("voxel_maxpool_fwd", feat), flag.data_ptr(), _stream(feat))
     return out
 
 
@@ -147,30 +130,6 @@ def voxel_maxpool_bwd(feat, ind, out, grad_out, grad_feat, out_size, scale):
                   grad_out.data_ptr(), _lib.i64_array(out.stride()), grad_feat.data_ptr(), bs, c, n, ind.shape[2],
                   _lib.i64_array(out_size), _lib.f32_array(scale), _dtype_code("voxel_maxpool_bwd", feat), _stream(feat))
     return grad_feat
-
-
-_deterministic = None
-
-
-def set_deterministic(flag):
-    """Explicit setting of ``is_deterministic`` (True / False), or None to hand the decision back to the environment.
-    Returns the previous explicit setting."""
-    global _deterministic
-    prev, _deterministic = _deterministic, (None if flag is None else bool(flag))
-    return prev
-
-
-def is_deterministic():
-    """Whether ``bilinear_gather_backward`` and ``msda_bwd`` (and so the autograd nodes over them) sum in a fixed order
-    (csrc/segsum.hip) when their ``deterministic`` argument is None.  Resolved on every call: the explicit
-    ``set_deterministic`` setting if there is one, else ``SMOS_DETERMINISTIC`` in the environment if it is set (default 0),
-    else ``torch.are_deterministic_algorithms_enabled()``."""
-    if _deterministic is not None:
-        return _deterministic
-    env = os.environ.get("SMOS_DETERMINISTIC")
-    if env is not None and env != "":
-        return env != "0"
-    return bool(torch.are_deterministic_algorithms_enabled())
 
 
 def segsum_chunk():
@@ -317,7 +276,7 @@ class _SegLoss(torch.autograd.Function):
         if need <= 0:
             raise RuntimeError("seg_loss: %d positions x %d classes is more than the sort is set up for" % (n, c))
         dev = pred.device
-        work = _stream_workspace("seg_loss", (need,), torch.uint8, dev)
+        work = shared.get("seg_loss", (need,), torch.uint8, dev)
         coef = torch.empty((c + 1, n), dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         stats = torch.empty(2, dtype=torch.float32, device=dev)
@@ -358,26 +317,6 @@ def seg_loss(pred, target, top_ratio=0.2, top_weight=4.0, ignore_index=0, lovasz
         return _SegLoss.apply(pred3, tgt, k, float(top_weight), int(ignore_index), float(lovasz_weight))
 
 
-_point_mlp_fused = None
-
-
-def set_point_mlp_fused(flag):
-    """Explicit setting of ``point_mlp_fused`` (True / False), or None to hand the decision back to the environment.
-    Returns the previous explicit setting."""
-    global _point_mlp_fused
-    prev, _point_mlp_fused = _point_mlp_fused, (None if flag is None else bool(flag))
-    return prev
-
-
-def point_mlp_fused():
-    """Whether PointNetStacker.forward (refapi/networks/backbone.py) may route a supported configuration to
-    ``point_mlp_train``: the ``set_point_mlp_fused`` setting if there is one, else ``SMOS_POINT_MLP`` in the environment
-    (default 0), read per call."""
-    if _point_mlp_fused is not None:
-        return _point_mlp_fused
-    return os.environ.get("SMOS_POINT_MLP", "0").strip().lower() not in ("", "0", "false", "off", "no")
-
-
 def point_mlp_chunk():
     """Points per chunk of partial sums of ``point_mlp_train`` (tests place their shapes around it)."""
     return _lib.query("smos_point_mlp_chunk")
@@ -398,7 +337,7 @@ class _PointMlpTrain(torch.autograd.Function):
         need = _lib.query("smos_point_mlp_work_bytes", s * n)
         if need <= 0:
             raise RuntimeError("point_mlp_train: %d x %d points is more than the kernels are set up for" % (s, n))
-        work = _stream_workspace("point_mlp", (need,), torch.uint8, dev)
+        work = shared.get("point_mlp", (need,), torch.uint8, dev)
         y = torch.empty((s, 64, n, 1), dtype=torch.float32, device=dev)
         fold = torch.empty(_lib.query("smos_point_mlp_fold_floats"), dtype=torch.float32, device=dev)
         dstat = torch.empty(_lib.query("smos_point_mlp_stat_doubles"), dtype=torch.float64, device=dev)
@@ -423,7 +362,7 @@ class _PointMlpTrain(torch.autograd.Function):
         grads = [torch.empty_like(p) if ctx.needs_input_grad[1 + i] else None for i, p in enumerate((g0, b0, w1, g1, b1, w2, g2, b2))]
         if any(g is not None for g in grads):
             need = _lib.query("smos_point_mlp_work_bytes", s * n)
-            work = _stream_workspace("point_mlp", (need,), torch.uint8, dev)
+            work = shared.get("point_mlp", (need,), torch.uint8, dev)
             with _on(dev), profiling.span_f("point_mlp_bwd[%dx%d]", (s, n)):
                 _lib.call("smos_point_mlp_bwd", x.data_ptr(), gy.data_ptr(), s, n, int(ctx.training), _point_mlp_ptrs(params),
                           _lib.f64_array(ctx.eps_mom), fold.data_ptr(), dstat.data_ptr(), _point_mlp_ptrs(grads), work.data_ptr(),
@@ -482,26 +421,6 @@ def point_mlp_train(x, bn0, conv1, bn1, conv2, bn2, training=None):
     return y
 
 
-_point_head_fused = None
-
-
-def set_point_head_fused(flag):
-    """Explicit setting of ``point_head_fused`` (True / False), or None to hand the decision back to the environment.
-    Returns the previous explicit setting."""
-    global _point_head_fused
-    prev, _point_head_fused = _point_head_fused, (None if flag is None else bool(flag))
-    return prev
-
-
-def point_head_fused():
-    """Whether ``backbone.point_head`` (refapi/networks/backbone.py) may route a supported CatFusion + PredBranch pair to
-    ``point_head_train``: the ``set_point_head_fused`` setting if there is one, else ``SMOS_POINT_HEAD_TRAIN`` in the
-    environment (default 0), read per call."""
-    if _point_head_fused is not None:
-        return _point_head_fused
-    return os.environ.get("SMOS_POINT_HEAD_TRAIN", "0").strip().lower() not in ("", "0", "false", "off", "no")
-
-
 def point_head_train_chunk():
     """Points per chunk of partial sums of ``point_head_train`` (tests place their shapes around it)."""
     return _lib.query("smos_point_head_train_chunk")
@@ -527,7 +446,7 @@ class _PointHeadTrain(torch.autograd.Function):
         bs, _, n = a.shape[:3]
         dev = a.device
         need = _lib.query("smos_point_head_train_work_bytes", bs * n)
-        work = _stream_workspace("point_head_train", (need,), torch.uint8, dev)
+        work = shared.get("point_head_train", (need,), torch.uint8, dev)
         logits = torch.empty((bs, 3, n, 1), dtype=torch.float32, device=dev)
         fold = torch.empty(_lib.query("smos_point_head_train_fold_floats"), dtype=torch.float32, device=dev)
         dstat = torch.empty(_lib.query("smos_point_head_train_stat_doubles"), dtype=torch.float64, device=dev)
@@ -555,7 +474,7 @@ class _PointHeadTrain(torch.autograd.Function):
         dp = [torch.empty_like(p) if ctx.needs_input_grad[3 + i] else None for i, p in enumerate(ctx.param_like)]
         if want_x or any(g is not None for g in dp):
             need = _lib.query("smos_point_head_train_work_bytes", bs * n)
-            work = _stream_workspace("point_head_train", (need,), torch.uint8, dev)
+            work = shared.get("point_head_train", (need,), torch.uint8, dev)
             pitch = _lib.i64_array([_point_head_pitch(t) for t in (a, b, c)])
             with _on(dev), profiling.span_f("point_head_bwd[%dx%d]", (bs, n)):
                 _lib.call("smos_point_head_train_bwd", a.data_ptr(), b.data_ptr(), c.data_ptr(), pitch, _ptr(masks), ctx.scale,
@@ -1859,28 +1778,8 @@ def upconv_xy_units(conv_a, bias, z1, z2, act, strip, max_blocks=0, out=None):
     return out
 
 
-_conv1_fused = None
-
-
-def set_conv1_fused(flag):
-    """Explicit setting of ``conv1_fused`` (True / False), or None to hand the decision back to the environment.
-    Returns the previous explicit setting."""
-    global _conv1_fused
-    prev, _conv1_fused = _conv1_fused, (None if flag is None else bool(flag))
-    return prev
-
-
-def conv1_fused():
-    """Whether ``CENet_Transformer.forward`` (refapi/networks/multi_view_encoder.py) may run the decoder's conv_1 on
-    ``upconv3x3_train``: the ``set_conv1_fused`` setting if there is one, else ``SMOS_CONV1_TRAIN`` in the environment
-    (default 0), read per call."""
-    if _conv1_fused is not None:
-        return _conv1_fused
-    return os.environ.get("SMOS_CONV1_TRAIN", "0").strip().lower() not in ("", "0", "false", "off", "no")
-
-
 # the layout upconv3x3_train returns: "cl" the channels-last-strided map its kernels write, "nchw" a contiguous copy of it
-# (a development knob for that one A/B, read once at import -- unlike the switch above, which is read per call; DESIGN.md
+# (a development knob for that one A/B, read once at import -- unlike conv1_fused, which is read per call; DESIGN.md
 # 4.9b has the measurement behind the default)
 _CONV1_OUT = os.environ.get("SMOS_CONV1_OUT", "cl")
 
@@ -2015,6 +1914,7 @@ def upconv3x3_train(conv_a, sources):
 
 
 STEM_TAPS = (1, 2, 2, 4)      # 3x3 taps that reach an output pixel under stride 2, per parity class (y&1)*2 + (x&1)
+_STEM_Y = ("stem_y0", "stem_y1", "stem_y2", "stem_y3")      # scratch tags of the per-class GEMM outputs
 
 
 def stem_prepare_weights(wa, wp):
@@ -2029,82 +1929,6 @@ def stem_prepare_weights(wa, wp):
         km = w.shape[0] // 32
         out.append(w.view(km, 32, 2, cin // 2).permute(0, 3, 2, 1).reshape(km, cin // 2, 64).contiguous())
     return out
-
-
-_stem_ws = {}
-
-
-def _stream_workspace(tag, shape, dtype, device, zero=False):
-    """Scratch of the sparse first stage, one flat buffer per (device, HIP stream, tag), grown to the largest request
-    seen: consecutive frames on a stream reuse it in stream order instead of holding a fresh allocation per frame that
-    the host has enqueued ahead of the GPU.  The returned view is valid until the next request with the same tag on the
-    same stream (callers consume it within the frame).  zero=True: zero-filled when (re)allocated -- for buffers whose
-    users leave them zero (the occupancy flags).  ``release_stream_workspaces`` frees them."""
-    key = (str(device), _raw_stream(_dev_index(device)), tag, dtype, _ws_namespace)
-    need = 1
-    for d in shape:
-        need *= int(d)
-    buf = _stem_ws.get(key)
-    if buf is None or buf.numel() < need:
-        buf = _stem_ws[key] = (torch.zeros if zero else torch.empty)(need, dtype=dtype, device=device)
-    return buf[:need].view(shape)
-
-
-class BlockScratch(dict):
-    """{(HIP stream, namespace): buffer} of one ChannelAtt block (engine._block_ws); a dict that can be weakly referenced,
-    so the registry below does not keep a dead engine's scratch alive."""
-    __slots__ = ("__weakref__", "device")
-    __hash__ = object.__hash__            # identity: the registry is a WeakSet
-    __eq__ = object.__eq__
-
-
-import weakref as _weakref
-
-_block_ws_tables = _weakref.WeakSet()
-_owner_tokens = iter(range(1, 1 << 62))
-
-
-def new_workspace_owner():
-    """A token for scratch namespaces that is never handed out twice (id(obj) can be: a later runner allocated at a freed
-    runner's address would alias its namespaces)."""
-    return next(_owner_tokens)
-
-
-def new_block_scratch(device=None):
-    table = BlockScratch()
-    table.device = None if device is None else str(device)
-    _block_ws_tables.add(table)
-    return table
-
-
-def release_stream_workspaces(device=None, stream=None, owner=None):
-    """Drops the per-stream scratch: all of it, one device's, one HIP stream's, or (owner = the token a graph runner put
-    into its namespace, ``new_workspace_owner``) what that runner's captured graphs use -- the sparse-stage buffers, the
-    scatter's flag words and the channel-attention blocks' plane sums alike.  StreamRunner.close() calls this."""
-    def owned(ns):
-        return isinstance(ns, tuple) and len(ns) > 1 and ns[1] == owner
-
-    def graph_ns(ns):
-        # scratch baked into some runner's captured graphs: only that runner (the owner path) may drop it -- torch hands
-        # pooled streams to several runners, so a stream handle alone does not say whose scratch an entry is
-        return isinstance(ns, tuple) and len(ns) > 1 and ns[0] == "graph"
-
-    def selected(dev, st, ns):
-        if owner is not None:
-            return owned(ns)
-        if (device is not None or stream is not None) and graph_ns(ns):
-            return False
-        return (device is None or dev is None or dev == str(device)) and (stream is None or st == stream)
-    for key in list(_stem_ws):                       # (device, stream, tag, dtype, namespace)
-        if selected(key[0], key[1], key[4]):
-            del _stem_ws[key]
-    for key in list(_flag_ws):                       # (device, stream, namespace)
-        if selected(str(key[0]), key[1], key[2]):
-            del _flag_ws[key]
-    for table in list(_block_ws_tables):             # engine._block_ws: {(stream, namespace): buffer} per ChannelAtt block
-        for key in list(table):
-            if selected(table.device, key[0], key[1]):
-                del table[key]
 
 
 class StemPlan:
@@ -2134,15 +1958,15 @@ def stem_plan(coord, h, w, row_floats=0):
     words = _lib.query("smos_stem_scan_state_words", cells)
     if words < 0:
         raise RuntimeError("stem_plan: grid too large for the scan")
-    flags = _stream_workspace("stem_flags", (cells,), torch.int32, dev, zero=True)      # left all-zero by the scan
-    state = _stream_workspace("stem_scan_state", (words,), torch.int64, dev)
-    row_cell = _stream_workspace("stem_row_cell", (cells,), torch.int32, dev)
-    row_of = _stream_workspace("stem_row_of", (cells,), torch.int32, dev)
-    meta = _stream_workspace("stem_meta", (12,), torch.int32, dev, zero=True)
+    flags = shared.get("stem_flags", (cells,), torch.int32, dev, zero=True)      # left all-zero by the scan
+    state = shared.get("stem_scan_state", (words,), torch.int64, dev)
+    row_cell = shared.get("stem_row_cell", (cells,), torch.int32, dev)
+    row_of = shared.get("stem_row_of", (cells,), torch.int32, dev)
+    meta = shared.get("stem_meta", (12,), torch.int32, dev, zero=True)
     rows = None
     if row_floats:
         # capacity: an occupied cell holds at least one point, so min(cells, points) rows always suffice
-        rows = _stream_workspace("stem_rows", (min(cells, b * t * n), row_floats), torch.float32, dev)
+        rows = shared.get("stem_rows", (min(cells, b * t * n), row_floats), torch.float32, dev)
     st = _stream(coord)
     with _on(dev), profiling.span_f("stem_mark+scan[%dx%dx%d]", (b, h, w)):
         _lib.call("smos_stem_mark", coord.data_ptr(), k, b, t, n, h, w, flags.data_ptr(), state.data_ptr(), st)
@@ -2191,8 +2015,8 @@ def sparse_downsample(src, plan, wprep, bias, compact, out=None):
         raise RuntimeError("sparse_downsample: the compact row table is [rows, Cin]")
     cout = bias.shape[0]
     per = b * (h // 2) * (w // 2)
-    ys = [_stream_workspace("stem_y%d" % k, (per, (taps + 1) * cout), torch.float32, dev)                # worst-case capacity
-          for k, taps in enumerate(STEM_TAPS)]
+    ys = [shared.get(tag, (per, (taps + 1) * cout), torch.float32, dev)                # worst-case capacity
+          for tag, taps in zip(_STEM_Y, STEM_TAPS)]
     if out is None:
         out = empty_cl(b, cout, (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1, dev)
     y_ptrs = (ctypes.c_void_p * 4)(*[y.data_ptr() for y in ys])

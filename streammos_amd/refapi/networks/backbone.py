@@ -4,8 +4,6 @@ Only the blocks reachable from the shipped configuration are provided (SURVEY.md
 Sub-module names and registration order reproduce the reference's ``state_dict`` keys exactly, which
 is what makes the 474-tensor checkpoint loadable with ``strict=True``; cited per class.
 """
-import os
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -224,9 +222,6 @@ def point_head(fusion, pred, *xs):
     return pred(fusion(*xs))
 
 
-_OWN_BACKWARD = os.environ.get("SMOS_BILINEAR_BWD", "1") != "0"    # A/B switch: 0 = training through F.grid_sample
-
-
 class BilinearSample(nn.Module):
     """Grid -> point bilinear gather, parameter-free -- networks/backbone.py:453-475.
 
@@ -244,7 +239,8 @@ class BilinearSample(nn.Module):
     def forward(self, grid_feat, grid_coord):
         grad_mode = torch.is_grad_enabled()
         coord_grad = grad_mode and grid_coord.requires_grad
-        own = not coord_grad and (_OWN_BACKWARD or not (grad_mode and grid_feat.requires_grad))
+        # ops.bilinear_bwd_own (SMOS_BILINEAR_BWD) is asked only where a backward would run; off = training through F.grid_sample
+        own = not coord_grad and (not (grad_mode and grid_feat.requires_grad) or ops.bilinear_bwd_own())
         if grid_feat.is_cuda and own and grid_coord.shape[-1] == 1 and grid_feat.dtype == torch.float32:
             return ops.bilinear_gather(grid_feat, grid_coord.float(), self.scale_rate).unsqueeze(-1)
         h, w = grid_feat.shape[2], grid_feat.shape[3]

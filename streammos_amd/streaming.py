@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, scratch
 
 VOTE_WINDOW = 8                      # frames_num_max, voxel_voting.py:140
 LEARNING_MAP_INV = {0: 0, 1: 9, 2: 251}   # config/StreamMOS.py:58
@@ -339,7 +339,7 @@ class _TwoStreamRunner:
             # the side stream must start behind the producers of next_dev.  Inputs made by upload() carry the event
             # recorded behind their H2D copies; anything else (e.g. device preprocessing on main) is ordered behind
             # main's whole tail.  Two encodes of one engine may run concurrently (frame 0: encode(t) on main beside
-            # encode(t+1) here): every piece of engine scratch is keyed by stream (engine._block_ws, ops._stream_workspace).
+            # encode(t+1) here): every piece of engine scratch is keyed by stream (scratch.Key).
             ready = next_dev.get("ready")
             if ready is not None:
                 self._side.wait_event(ready)
@@ -441,7 +441,7 @@ class StreamRunner(_TwoStreamRunner):
         self.use_graph = graph
         self.split = max(1, int(split))
         self._graphs = self._groups = self._g_shape = self._g_pred = self._g_engine = None      # set by _capture
-        self._ws_owner = ops.new_workspace_owner()      # names this runner's scratch namespaces (never reused, unlike id())
+        self._ws_owner = scratch.new_workspace_owner()  # names this runner's scratch namespaces (never reused, unlike id())
         self._pre = None                # step_raw: the DevicePreprocessor of the frame_point_num in use
         self._uploads = ScanUploads(self.device)
         self._raw_ahead = None          # step_raw: (current scan of the window prepared ahead, its inputs)
@@ -462,10 +462,7 @@ class StreamRunner(_TwoStreamRunner):
         per = v // k
         self._groups = []
         side = torch.cuda.Stream(self.device)
-        try:
-            self._capture_groups(dev, eng, k, per, side)
-        finally:
-            ops.set_workspace_namespace(0)
+        self._capture_groups(dev, eng, k, per, side)
         self._g_shape = tuple(dev["pcds_xyzi"].shape)
         self._g_pred = torch.empty((v,) + tuple(self._groups[0]["graphs"][True][1].shape[1:]), dtype=torch.float32,
                                    device=self.device)
@@ -474,30 +471,31 @@ class StreamRunner(_TwoStreamRunner):
     def _capture_groups(self, dev, eng, k, per, side):
         for gi in range(k):
             sl = slice(gi * per, (gi + 1) * per)
-            ops.set_workspace_namespace(("graph", self._ws_owner, gi))    # per-group scratch: the groups' graphs replay concurrently
-            g_in = {key: dev[key][sl].clone() for key in _KEYS}
-            batch = {key: g_in[key].unsqueeze(0) for key in _KEYS}
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side), torch.no_grad():
-                # eager warm-up on a side stream: MIOpen algorithm search, lazy engine build, allocator pools
-                mem = None
-                for _ in range(2):
-                    mem = self.model.infer(batch, 0, None)[-1]
-                g_mem = mem.clone()
-                for _ in range(2):
-                    self.model.infer(batch, 1, g_mem)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            torch.cuda.synchronize(self.device)
-            graphs = {}
-            for first in (True, False):
-                g = torch.cuda.CUDAGraph()
-                with torch.no_grad(), torch.cuda.graph(g):
-                    res = self.model.infer(batch, 0 if first else 1, None if first else g_mem)
-                    pred, mem = res[0], res[-1]
-                    g_mem.copy_(mem)
-                graphs[first] = (g, pred)
-            self._groups.append({"in": g_in, "mem": g_mem, "graphs": graphs, "slice": sl,
-                                 "stream": torch.cuda.Stream(self.device)})
+            # per-group scratch: the groups' graphs replay concurrently
+            with scratch.namespace(scratch.GraphNamespace(self._ws_owner, gi)):
+                g_in = {key: dev[key][sl].clone() for key in _KEYS}
+                batch = {key: g_in[key].unsqueeze(0) for key in _KEYS}
+                side.wait_stream(torch.cuda.current_stream(self.device))
+                with torch.cuda.stream(side), torch.no_grad():
+                    # eager warm-up on a side stream: MIOpen algorithm search, lazy engine build, allocator pools
+                    mem = None
+                    for _ in range(2):
+                        mem = self.model.infer(batch, 0, None)[-1]
+                    g_mem = mem.clone()
+                    for _ in range(2):
+                        self.model.infer(batch, 1, g_mem)
+                torch.cuda.current_stream(self.device).wait_stream(side)
+                torch.cuda.synchronize(self.device)
+                graphs = {}
+                for first in (True, False):
+                    g = torch.cuda.CUDAGraph()
+                    with torch.no_grad(), torch.cuda.graph(g):
+                        res = self.model.infer(batch, 0 if first else 1, None if first else g_mem)
+                        pred, mem = res[0], res[-1]
+                        g_mem.copy_(mem)
+                    graphs[first] = (g, pred)
+                self._groups.append({"in": g_in, "mem": g_mem, "graphs": graphs, "slice": sl,
+                                     "stream": torch.cuda.Stream(self.device)})
 
     def _replay(self, dev):
         main = torch.cuda.current_stream(self.device)
@@ -525,7 +523,7 @@ class StreamRunner(_TwoStreamRunner):
             self.voter.reset()
 
     def close(self):
-        """Frees the per-stream scratch this runner's HIP streams hold (ops._stream_workspace: ~1.2 GB per stream at the
+        """Frees the per-stream scratch this runner's HIP streams hold (scratch.shared: ~1.2 GB per stream at the
         validation shape), the look-ahead, the cache of uploaded scans and the pinned staging ring.  The runner stays usable
         and keeps its place in the sequence; all of it is re-allocated on the next frame."""
         self._pending = self._raw_ahead = None

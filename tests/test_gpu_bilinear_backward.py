@@ -190,7 +190,7 @@ def test_autograd_of_a_sum_has_an_expanded_gradient():
     _check("autograd c32/runs sum()", grid.grad, types.SimpleNamespace(S=s, A=a, m=m))
 
 
-def test_module_in_training_mode_takes_the_own_path(monkeypatch):
+def test_module_in_training_mode_takes_the_own_path(monkeypatch, request):
     """BilinearSample with the switch at 1 on a grid that needs a gradient: forward and backward on the own kernels (counted on ops), the
     gradient against the F.grid_sample formulation the switch at 0 keeps, inside the sum of both bounds.  The case is
     dyadic (tests/bilinear_bwd_cases.py::dyadic_case), so both sample the same positions."""
@@ -205,7 +205,7 @@ def test_module_in_training_mode_takes_the_own_path(monkeypatch):
         return wrapped
     monkeypatch.setattr(ops, "bilinear_gather", count("fwd", fwd))
     monkeypatch.setattr(ops, "bilinear_gather_backward", count("bwd", bwd))
-    monkeypatch.setattr(backbone, "_OWN_BACKWARD", True)                                 # SMOS_BILINEAR_BWD=1
+    request.addfinalizer(lambda prev=ops.set_bilinear_bwd_own(True): ops.set_bilinear_bwd_own(prev))     # SMOS_BILINEAR_BWD=1
     mod = backbone.BilinearSample(case.c, case.scale).train()
     feat = torch.randn((case.b, case.c, case.h, case.w), device=DEV)
     coord = _t(case.coord[..., :2]).unsqueeze(-1)                                        # (BS, N, 2, 1)
@@ -228,12 +228,12 @@ def test_module_in_training_mode_takes_the_own_path(monkeypatch):
     assert (diff <= 2.0 * cases.bound(case)).all()
 
     # the switch at 0, and a coordinate gradient whatever the switch: F.grid_sample as before
-    monkeypatch.setattr(backbone, "_OWN_BACKWARD", False)
+    ops.set_bilinear_bwd_own(False)
     off = feat.clone().requires_grad_()
     mod(off, coord).backward(go)
     assert calls == {"fwd": 1, "bwd": 1}
     _check("module dyadic switch 0", off.grad, case)
-    monkeypatch.setattr(backbone, "_OWN_BACKWARD", True)
+    ops.set_bilinear_bwd_own(True)
     cg = coord.clone().requires_grad_()
     mod(feat.clone().requires_grad_(), cg).backward(go)
     assert calls == {"fwd": 1, "bwd": 1} and cg.grad is not None

@@ -266,14 +266,14 @@ class _CountingLib:
         return counted
 
 
-def test_bilinear_module_through_autograd(monkeypatch, chunk):
+def test_bilinear_module_through_autograd(monkeypatch, request, chunk):
     """BilinearSample in training mode with the setting on: the fixed-order entry, the same bits on two runs and the bits of
     the direct op; with the setting off the atomic entry."""
     key = ("dyadic",)
     case = cases.bilinear_case(key)
     lib = _CountingLib(_lib.load())
     monkeypatch.setattr(_lib, "_lib", lib)
-    monkeypatch.setattr(backbone, "_OWN_BACKWARD", True)
+    request.addfinalizer(lambda prev=ops.set_bilinear_bwd_own(True): ops.set_bilinear_bwd_own(prev))
     monkeypatch.delenv("SMOS_DETERMINISTIC", raising=False)
     mod = backbone.BilinearSample(case.c, case.scale).train()
     feat = torch.randn((case.b, case.c, case.h, case.w), device=DEV)

@@ -32,7 +32,7 @@ import numpy as np
 import pytest
 import torch
 
-from streammos_amd import ops
+from streammos_amd import ops, scratch
 from tests import util
 
 pytestmark = pytest.mark.gpu
@@ -45,7 +45,7 @@ def _t(a, dtype=torch.float32):
 
 
 def _flags_all_zero():
-    bufs = [buf for key, buf in ops._stem_ws.items() if key[2] == "stem_flags"]
+    bufs = [buf for _, buf in scratch.entries("stem_flags")]
     return len(bufs) > 0 and not any(bool(buf.any()) for buf in bufs)
 
 

@@ -566,33 +566,3 @@ def test_bench_roofline_picks_the_dominant_kernel_family_not_a_label():
     ctx = {"stem_rows": 200000, "stem_class_rows": (50000, 50000, 50000, 50000)}
     assert bench.algorithmic_flops("stem_gemm[4x512x512x192]", ctx) == 2 * 50000 * 192 * 32 * (2 + 3 + 3 + 5)
     assert bench.algorithmic_flops("stem_gemm[4x512x512x192]") == 0
-
-
-def test_release_stream_workspaces_filters_by_device_and_spares_graph_namespaces():
-    """ops.release_stream_workspaces: a (device, stream) release drops that device's eager scratch only -- block
-    tables of another device and entries baked into a runner's captured graphs (namespace ('graph', owner, group)) stay; the
-    owner path drops exactly that runner's."""
-    from streammos_amd import ops
-    saved = (dict(ops._stem_ws), dict(ops._flag_ws))
-    ops._stem_ws.clear()
-    ops._flag_ws.clear()
-    try:
-        t0, t1 = ops.new_block_scratch("cuda:0"), ops.new_block_scratch("cuda:1")
-        for t in (t0, t1):
-            t[(111, 0)] = "eager"
-            t[(111, ("graph", 7, 0))] = "graph7"
-            t[(222, 0)] = "other stream"
-        ops._stem_ws[("cuda:0", 111, "stem_rows", None, 0)] = 1
-        ops._stem_ws[("cuda:1", 111, "stem_rows", None, 0)] = 2
-        ops._stem_ws[("cuda:0", 111, "stem_rows", None, ("graph", 7, 1))] = 3
-        ops.release_stream_workspaces("cuda:0", 111)
-        assert sorted(map(str, t0)) == sorted(map(str, [(111, ("graph", 7, 0)), (222, 0)])) and len(t1) == 3
-        assert sorted(ops._stem_ws.values()) == [2, 3]
-        ops.release_stream_workspaces(owner=7)
-        assert list(t0) == [(222, 0)] and sorted(map(str, t1)) == sorted(map(str, [(111, 0), (222, 0)]))
-        assert list(ops._stem_ws.values()) == [2]
-        ops.release_stream_workspaces()
-        assert not t0 and not t1 and not ops._stem_ws
-    finally:
-        ops._stem_ws.update(saved[0])
-        ops._flag_ws.update(saved[1])

@@ -100,7 +100,8 @@ def test_basic_block(use_att):
         assert p.cw1.is_contiguous() and p.cw2.is_contiguous()
     else:
         assert p.cw1 is None and p.cb1 is None and p.cw2 is None and p.cb2 is None
-    assert p.plan is None and p.scratch is None         # made by the first block call / the first gated call
+    assert p.plan is None                               # made by the first block call
+    assert type(p.tag) is int if use_att else p.tag is None     # a gated block's slot in the engine's scratch table
     with pytest.raises(AttributeError):
         p.wq = None
 

@@ -114,9 +114,9 @@ def test_work_bytes_queries():
     assert msda(2, 100, 0, 32, 2, 7, 4) == -1
 
 
-def test_is_deterministic_resolution_order(monkeypatch):
+def test_is_deterministic_resolution_order(monkeypatch, request):
     """The explicit setting, then SMOS_DETERMINISTIC, then torch's flag; every call looks again."""
-    monkeypatch.setattr(ops, "_deterministic", None)
+    request.addfinalizer(lambda prev=ops.set_deterministic(None): ops.set_deterministic(prev))
     monkeypatch.delenv("SMOS_DETERMINISTIC", raising=False)
     flag = {"v": False}
     monkeypatch.setattr(torch, "are_deterministic_algorithms_enabled", lambda: flag["v"])

@@ -145,7 +145,6 @@ def step_child(reps, contiguous):
     from streammos_amd import ops, synth
     from streammos_amd.refapi.config import StreamMOS as cfg
     from streammos_amd.refapi.models import StreamMOS
-    from streammos_amd.refapi.networks import backbone
     model = StreamMOS.AttNet(cfg.get_config()[2])
     model.load_state_dict(synth.seeded_state_dict(model.state_dict()), strict=True)
     model = model.to(DEV).train()
@@ -177,7 +176,7 @@ def step_child(reps, contiguous):
     loss = step()
     per_step = calls["bwd"]
     ms = measure(step, reps, iters=1, warm=2)
-    print(json.dumps({"switch": int(backbone._OWN_BACKWARD), "contiguous": bool(contiguous), "ms": ms, "loss": float(loss.item()),
+    print(json.dumps({"switch": int(ops.bilinear_bwd_own()), "contiguous": bool(contiguous), "ms": ms, "loss": float(loss.item()),
                       "own_backward_calls_per_step": per_step, "peak_gb": torch.cuda.max_memory_allocated() / 2 ** 30}), flush=True)
 
 
