@@ -13,9 +13,8 @@
 // dW1 96x192) go through v_mfma_f32_32x32x2_f32 with the points on K: a wave's 64 points are staged point-major in LDS and
 // every wave of the block accumulates its own 32x32 tiles of the result over all staged points.
 //
-// Reductions: no float atomics.  Points are cut into chunks of kPhChunk (a constant); whichever block walks a chunk forms
-// its partial sums in a fixed lane / wave / trip order; the partials are summed per group of kPhGroup chunks in chunk order
-// in float64 and the groups in order in float64.  The bits of every result depend on the data alone.
+// Reductions: the fixed-order sums of csrc/chunk_sums.h over chunks of kPhChunk = 1024 points; the bits of every result
+// depend on the data alone.
 //
 // Accuracy: layer 1 runs on xt - xt(first point), so z1 is formed about its value at the first point from differences
 // of the inputs; the z2 sums are taken about z2 at the first point; both are corrected in float64.  In the chain a mean is
@@ -25,6 +24,7 @@
 // bit j & 31 of word 6 + (j >> 5) keeps channel j of the second dropout.  Generated bits: Philox4x32-10 with key = the two
 // halves of seed[0] and counter (p, 8 w + i, lo(seed[1]), hi(seed[1])); output word v of call i decides bit 4 i + v; a bit
 // is kept iff its 32-bit draw is below kKeepBelow = 3435973837 = ceil(0.8 * 2^32), a keep probability of 0.8 + 4.7e-11.
+#include "chunk_sums.h"
 #include "philox.h"
 
 namespace smos {
@@ -33,7 +33,6 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kPhChunk = 1024;                 // points per chunk of partial sums
-constexpr int kPhGroup = 64;                   // chunks per first-level float64 sum
 constexpr int kPhBlock = 256;
 constexpr int kK = 192, kM1 = 96, kM2 = 64, kM3 = 3;
 constexpr uint32_t kKeepBelow = 3435973837u;
@@ -57,9 +56,8 @@ enum : int {
 };
 // float64 statistics the forward leaves: mean and biased variance of z1 and z2 as normalised with
 enum : int { D_MU1 = 0, D_VAR1 = kM1, D_MU2 = 2 * kM1, D_VAR2 = 2 * kM1 + kM2, D_END = 2 * kM1 + 2 * kM2 };
-// work buffer: coefficients of the backward (doubles: dbeta / P and dgamma / P of both batch norms), then the partials
+// work buffer: the coefficients of the backward are doubles, dbeta / P and dgamma / P of both batch norms
 enum : int { C_B2 = 0, C_G2 = kM2, C_B1 = 2 * kM2, C_G1 = 2 * kM2 + kM1 };
-constexpr int64_t kWPart = 4096;
 
 struct PhIn {
   const float* xa; const float* xb; const float* xc;   // [B,64,N] with channel pitch pa / pb / pc
@@ -76,40 +74,13 @@ struct PhParams {
   double eps[2], mom[2];
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-__device__ __forceinline__ double total(const double* __restrict__ gsum, int64_t ngroups, int cols, int col) {
-  double s = 0.0;
-  for (int64_t g = 0; g < ngroups; ++g) s += gsum[g * cols + col];
-  return s;
-}
-
-struct PhPoint {
-  bool live;
-  int64_t pc;   // the point, clamped onto the last one past the end (its loads are valid, its contributions selected away)
-  int64_t s, n;
-};
-
-__device__ __forceinline__ PhPoint ph_point(int64_t p, int64_t P, int64_t N) {
-  PhPoint r;
-  r.live = p < P;
-  r.pc = r.live ? p : P - 1;
-  r.s = (int64_t)((uint32_t)r.pc / (uint32_t)N);      // P < 2^31
-  r.n = r.pc - r.s * N;
-  return r;
-}
-
 // eight input channels of a point and their keep bits: group g = channels [8 g, 8 g + 8) of the concatenation
 struct PhX {
   float v[8];
   uint32_t m;
 };
 
-__device__ __forceinline__ void ph_load8(const PhIn& in, const PhPoint& pt, int g, PhX& o) {
+__device__ __forceinline__ void ph_load8(const PhIn& in, const ChunkPoint& pt, int g, PhX& o) {
   const int i = g >> 3;
   const float* base = i == 0 ? in.xa : i == 1 ? in.xb : in.xc;
   const int64_t pitch = i == 0 ? in.pa : i == 1 ? in.pb : in.pc;
@@ -126,7 +97,7 @@ __device__ __forceinline__ float ph_xt(const PhIn& in, const PhX& x, int c) { re
 // z1c = W1 (xt - xt0) = z1 - z1(first point), the next group's loads in flight behind the current group's 8 x 96 FMAs.  The
 // difference is taken on the inputs: a channel with mean 1000 and spread 0.01 enters at its spread, so z1c is as exact as
 // its own size allows and the mean that BN1 subtracts (fold: the mean of z1c, or running_mean - z1(first point)) is small.
-__device__ __forceinline__ void ph_z1(const PhIn& in, const float* __restrict__ fold, const PhPoint& pt, float (&z)[kM1]) {
+__device__ __forceinline__ void ph_z1(const PhIn& in, const float* __restrict__ fold, const ChunkPoint& pt, float (&z)[kM1]) {
 #pragma unroll
   for (int j = 0; j < kM1; ++j) z[j] = 0.0f;
   PhX cur, nxt;
@@ -165,7 +136,7 @@ __device__ __forceinline__ float ph_z2(const float* __restrict__ wr, const float
 // keep bit j of the second dropout from the point's two words
 __device__ __forceinline__ bool ph_keep2(uint32_t m0, uint32_t m1, int j) { return (((j < 32 ? m0 : m1) >> (j & 31)) & 1u) != 0; }
 
-__device__ __forceinline__ void ph_mask2(const PhIn& in, const PhPoint& pt, uint32_t& m0, uint32_t& m1) {
+__device__ __forceinline__ void ph_mask2(const PhIn& in, const ChunkPoint& pt, uint32_t& m0, uint32_t& m1) {
   m0 = m1 = 0xffffffffu;
   if (in.mask) {
     m0 = in.mask[6 * in.P + pt.pc];
@@ -213,7 +184,7 @@ __global__ __launch_bounds__(256) void ph_pass(PhIn in, const float* __restrict_
     for (int t = 0; t < kPhChunk / kPhBlock; ++t) {
       const int64_t tile0 = chunk * kPhChunk + t * kPhBlock;
       if (tile0 >= P) break;
-      const PhPoint pt = ph_point(MODE == 2 ? 0 : tile0 + tid, P, N);
+      const ChunkPoint pt = chunk_point(MODE == 2 ? 0 : tile0 + tid, P, N);
       float z[kM1];
       ph_z1(in, fold, pt, z);
       if (MODE == 1) {
@@ -298,38 +269,18 @@ __global__ __launch_bounds__(256) void ph_pass(PhIn in, const float* __restrict_
         red[wave][64 + lane] = acc[2];
         red[wave][kM1 + 64 + lane] = acc[3];
       }
-      __syncthreads();
-      if (tid < kColsS1) partial[chunk * kColsS1 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-      __syncthreads();
+      block_columns_store<kColsS1>(red, partial, chunk, tid);
     } else if (MODE == 3) {
       red[wave][lane] = acc[0];
       red[wave][kM2 + lane] = acc[1];
-      __syncthreads();
-      if (tid < kColsS2) partial[chunk * kColsS2 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-      __syncthreads();
+      block_columns_store<kColsS2>(red, partial, chunk, tid);
     } else if (MODE == 5) {
 #pragma unroll
       for (int i = 0; i < 5; ++i) red[wave][i * 64 + lane] = acc[i];
       if (lane < 4) red[wave][320 + lane] = acc[5];
-      __syncthreads();
-      for (int i = tid; i < kColsB1; i += kPhBlock) partial[chunk * kColsB1 + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-      __syncthreads();
+      block_columns_store<kColsB1>(red, partial, chunk, tid);
     }
   }
-}
-
-// first-level sums: one thread per (group of kPhGroup chunks, column), chunks in order
-template <typename T>
-__global__ __launch_bounds__(256) void ph_group_sum(const T* __restrict__ partial, int64_t nchunks, int cols, double* __restrict__ gsum) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t ngroups = (nchunks + kPhGroup - 1) / kPhGroup;
-  if (i >= ngroups * cols) return;
-  const int64_t grp = i / cols;
-  const int col = (int)(i - grp * cols);
-  const int64_t c0 = grp * kPhGroup, c1 = c0 + kPhGroup < nchunks ? c0 + kPhGroup : nchunks;
-  double s = 0.0;
-  for (int64_t c = c0; c < c1; ++c) s += (double)partial[c * cols + col];
-  gsum[i] = s;
 }
 
 // BN statistics of layer L (1 or 2): training from the sums about the shift, the running buffers updated; eval from the
@@ -349,20 +300,15 @@ __global__ __launch_bounds__(128) void ph_fin_stats(int layer, int training, con
   }
   double mu, var;
   if (training) {
-    const double s1 = total(gsum, ngroups, 2 * M, j) / (double)P, s2 = total(gsum, ngroups, 2 * M, M + j) / (double)P;
-    mu = shift + s1;
-    var = s2 - s1 * s1;
-    var = var > 0.0 ? var : 0.0;
-    rm[j] = (float)((1.0 - mom) * (double)rm[j] + mom * mu);
-    rv[j] = (float)((1.0 - mom) * (double)rv[j] + mom * (var * ((double)P / (double)(P - 1))));
+    bn_stats_about_shift(gsum, ngroups, M, j, P, &mu, &var);
+    mu += shift;
+    bn_running_update(rm, rv, j, mom, mu, var, P);
   } else {
     mu = (double)rm[j];
     var = (double)rv[j];
   }
   const double sub = layer == 1 ? mu - shift : mu;       // what the chain subtracts: layer 1 works about the shift
-  const float hi = (float)sub;
-  fold[(layer == 1 ? F_MU1H : F_MU2H) + j] = hi;
-  fold[(layer == 1 ? F_MU1L : F_MU2L) + j] = (float)(sub - (double)hi);
+  split_hi_lo(sub, &fold[(layer == 1 ? F_MU1H : F_MU2H) + j], &fold[(layer == 1 ? F_MU1L : F_MU2L) + j]);
   fold[(layer == 1 ? F_R1 : F_R2) + j] = (float)(1.0 / sqrt(var + eps));
   dstat[(layer == 1 ? D_MU1 : D_MU2) + j] = mu;
   dstat[(layer == 1 ? D_VAR1 : D_VAR2) + j] = var;
@@ -405,7 +351,7 @@ __global__ __launch_bounds__(256) void ph_bwd(PhIn in, const float* __restrict__
     for (int t = 0; t < kPhChunk / kPhBlock; ++t) {
       const int64_t tile0 = chunk * kPhChunk + t * kPhBlock;
       if (tile0 >= P) break;
-      const PhPoint pt = ph_point(tile0 + tid, P, N);
+      const ChunkPoint pt = chunk_point(tile0 + tid, P, N);
       float zh[kM1], h[kM1], da1[kM1];
       ph_z1(in, fold, pt, zh);
       ph_zhat1(fold, zh);
@@ -642,24 +588,8 @@ __global__ __launch_bounds__(256) void ph_masks(const uint8_t* __restrict__ keep
   masks[i] = bits;
 }
 
-int64_t ph_chunks(int64_t P) { return (P + kPhChunk - 1) / kPhChunk; }
-int64_t ph_groups(int64_t P) { return (ph_chunks(P) + kPhGroup - 1) / kPhGroup; }
-int64_t ph_part_bytes(int64_t P) { return ph_chunks(P) * kColsB3 * 4; }      // the widest partial row: pass 3 of the backward
-
-template <typename T>
-int ph_launch_group_sum(const T* partial, int64_t nchunks, int cols, double* gsum, hipStream_t s) {
-  const int64_t items = ((nchunks + kPhGroup - 1) / kPhGroup) * cols;
-  hipLaunchKernelGGL((ph_group_sum<T>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, partial, nchunks, cols, gsum);
-  return check_launch("point_head_train group sum");
-}
-
-int ph_grid(const void* fn, size_t lds, int64_t nchunks, const char* what, int64_t* grid) {
-  KernelSetup ks;
-  if (int rc = kernel_setup(fn, lds, kPhBlock, &ks, what)) return rc;
-  const int64_t resident = conv_grid_cap((int64_t)(ks.per_cu > 0 ? ks.per_cu : 1) * (ks.cus > 0 ? ks.cus : 1));   // (the test hook's cap: several chunks per block)
-  *grid = nchunks < resident ? nchunks : resident;
-  return SMOS_OK;
-}
+// the widest partial row is pass 3 of the backward
+ChunkWork ph_work(void* work, int64_t P) { return chunk_work(work, P, kPhChunk, kColsB3); }
 
 int ph_params(const void* const* p, const double* eps_mom, PhParams* q) {
   for (int i = 0; i < 12; ++i) SMOS_REQUIRE(p[i], "point_head_train: null parameter pointer %d", i);
@@ -696,14 +626,10 @@ extern "C" int32_t smos_point_head_train_fold_floats(void) { return F_END; }
 extern "C" int32_t smos_point_head_train_stat_doubles(void) { return D_END; }
 
 extern "C" int64_t smos_point_head_train_work_bytes(int64_t P) {
-  if (P < 1 || P >= (1LL << 31) - kPhChunk) return -1;
-  return kWPart + ph_part_bytes(P) + ph_groups(P) * kColsB3 * 8;
+  return ph_work(nullptr, P).bytes;
 }
 
-extern "C" int64_t smos_point_head_train_mask_words(int64_t P) {
-  if (P < 1 || P >= (1LL << 31) - kPhChunk) return -1;
-  return 8 * P;
-}
+extern "C" int64_t smos_point_head_train_mask_words(int64_t P) { return ph_work(nullptr, P).bytes < 0 ? -1 : 8 * P; }
 
 extern "C" int smos_point_head_train_masks(const uint8_t* keep1, const uint8_t* keep2, const int64_t* seed, int64_t B, int64_t N,
                                            uint32_t* masks, smos_stream_t stream) {
@@ -722,32 +648,30 @@ extern "C" int smos_point_head_train_fwd(const float* a, const float* b, const f
   if (int rc = ph_inputs("point_head_train_fwd", a, b, c, pitch, masks, scale, B, N, &in)) return rc;
   SMOS_REQUIRE(params && eps_mom && logits && fold && dstat && work, "point_head_train_fwd: null pointer");
   const int64_t P = in.P;
-  const int64_t need = smos_point_head_train_work_bytes(P);
-  SMOS_REQUIRE(need > 0 && work_bytes >= need, "point_head_train_fwd: %lld points need %lld bytes of work space, got %lld", (long long)P,
-               (long long)need, (long long)work_bytes);
+  const ChunkWork w = ph_work(work, P);
+  if (int rc = chunk_work_check(w, P, work_bytes, "point_head_train_fwd")) return rc;
   SMOS_REQUIRE(!training || P > 1, "point_head_train_fwd: batch statistics need more than one point");
   PhParams q;
   if (int rc = ph_params(params, eps_mom, &q)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t nchunks = ph_chunks(P), ngroups = ph_groups(P);
-  double* partial = reinterpret_cast<double*>(static_cast<char*>(work) + kWPart);
-  double* gsum = reinterpret_cast<double*>(static_cast<char*>(work) + kWPart + ph_part_bytes(P));
+  const int64_t nchunks = w.nchunks, ngroups = w.ngroups;
+  double* partial = reinterpret_cast<double*>(w.part);
   int64_t grid = 1;
   hipLaunchKernelGGL(ph_prep, dim3((kM1 * kK + 255) / 256), dim3(256), 0, s, q, in, fold);
   if (training) {
-    if (int rc = ph_grid(reinterpret_cast<const void*>(&ph_pass<1>), 0, nchunks, "point_head_train z1 sums", &grid)) return rc;
+    if (int rc = chunk_grid(reinterpret_cast<const void*>(&ph_pass<1>), 0, kPhBlock, nchunks, "point_head_train z1 sums", &grid)) return rc;
     hipLaunchKernelGGL((ph_pass<1>), dim3((unsigned)grid), dim3(kPhBlock), 0, s, in, fold, nullptr, nullptr, nullptr, partial, nchunks);
-    if (int rc = ph_launch_group_sum(partial, nchunks, kColsS1, gsum, s)) return rc;
+    if (int rc = launch_group_sum(partial, nchunks, kColsS1, w.gsum, s, "point_head_train group sum")) return rc;
   }
-  hipLaunchKernelGGL(ph_fin_stats, dim3(1), dim3(128), 0, s, 1, (int)training, gsum, ngroups, P, q, fold, dstat);
+  hipLaunchKernelGGL(ph_fin_stats, dim3(1), dim3(128), 0, s, 1, (int)training, w.gsum, ngroups, P, q, fold, dstat);
   if (training) {
-    if (int rc = ph_grid(reinterpret_cast<const void*>(&ph_pass<3>), 0, nchunks, "point_head_train z2 sums", &grid)) return rc;
+    if (int rc = chunk_grid(reinterpret_cast<const void*>(&ph_pass<3>), 0, kPhBlock, nchunks, "point_head_train z2 sums", &grid)) return rc;
     hipLaunchKernelGGL((ph_pass<2>), dim3(1), dim3(64), 0, s, in, fold, fold + F_SH2, nullptr, nullptr, nullptr, (int64_t)1);
     hipLaunchKernelGGL((ph_pass<3>), dim3((unsigned)grid), dim3(kPhBlock), 0, s, in, fold, nullptr, nullptr, nullptr, partial, nchunks);
-    if (int rc = ph_launch_group_sum(partial, nchunks, kColsS2, gsum, s)) return rc;
+    if (int rc = launch_group_sum(partial, nchunks, kColsS2, w.gsum, s, "point_head_train group sum")) return rc;
   }
-  hipLaunchKernelGGL(ph_fin_stats, dim3(1), dim3(128), 0, s, 2, (int)training, gsum, ngroups, P, q, fold, dstat);
-  if (int rc = ph_grid(reinterpret_cast<const void*>(&ph_pass<4>), 0, nchunks, "point_head_train logits", &grid)) return rc;
+  hipLaunchKernelGGL(ph_fin_stats, dim3(1), dim3(128), 0, s, 2, (int)training, w.gsum, ngroups, P, q, fold, dstat);
+  if (int rc = chunk_grid(reinterpret_cast<const void*>(&ph_pass<4>), 0, kPhBlock, nchunks, "point_head_train logits", &grid)) return rc;
   hipLaunchKernelGGL((ph_pass<4>), dim3((unsigned)grid), dim3(kPhBlock), 0, s, in, fold, nullptr, nullptr, logits, nullptr, nchunks);
   return check_launch("point_head_train_fwd");
 }
@@ -762,9 +686,8 @@ extern "C" int smos_point_head_train_bwd(const float* a, const float* b, const f
   if (int rc = ph_inputs("point_head_train_bwd", a, b, c, pitch, masks, scale, B, N, &in)) return rc;
   SMOS_REQUIRE(grad_logits && fold && grads && work, "point_head_train_bwd: null pointer");
   const int64_t P = in.P;
-  const int64_t need = smos_point_head_train_work_bytes(P);
-  SMOS_REQUIRE(need > 0 && work_bytes >= need, "point_head_train_bwd: %lld points need %lld bytes of work space, got %lld", (long long)P,
-               (long long)need, (long long)work_bytes);
+  const ChunkWork w = ph_work(work, P);
+  if (int rc = chunk_work_check(w, P, work_bytes, "point_head_train_bwd")) return rc;
   float* dxa = (float*)grads[0];
   float* dxb = (float*)grads[1];
   float* dxc = (float*)grads[2];
@@ -777,32 +700,31 @@ extern "C" int smos_point_head_train_bwd(const float* a, const float* b, const f
   const int need_p1 = (o.w3 || o.b3 || o.g2 || o.be2 || (training && (need_p2 || need_p3))) ? 1 : 0;
   if (!need_p1 && !need_p2 && !need_p3) return SMOS_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t nchunks = ph_chunks(P), ngroups = ph_groups(P);
-  double* coef = reinterpret_cast<double*>(work);
-  char* part = static_cast<char*>(work) + kWPart;
-  double* gsum = reinterpret_cast<double*>(part + ph_part_bytes(P));
+  const int64_t nchunks = w.nchunks, ngroups = w.ngroups;
+  double* coef = static_cast<double*>(w.coef);
+  char* part = w.part;
   int64_t grid = 1;
   if (need_p1) {
-    if (int rc = ph_grid(reinterpret_cast<const void*>(&ph_pass<5>), 0, nchunks, "point_head_train backward pass 1", &grid)) return rc;
+    if (int rc = chunk_grid(reinterpret_cast<const void*>(&ph_pass<5>), 0, kPhBlock, nchunks, "point_head_train backward pass 1", &grid)) return rc;
     hipLaunchKernelGGL((ph_pass<5>), dim3((unsigned)grid), dim3(kPhBlock), 0, s, in, fold, nullptr, grad_logits, nullptr,
                        reinterpret_cast<double*>(part), nchunks);
-    if (int rc = ph_launch_group_sum(reinterpret_cast<const double*>(part), nchunks, kColsB1, gsum, s)) return rc;
+    if (int rc = launch_group_sum(reinterpret_cast<const double*>(part), nchunks, kColsB1, w.gsum, s, "point_head_train group sum")) return rc;
   }
-  hipLaunchKernelGGL(ph_fin_b1, dim3(1), dim3(256), 0, s, need_p1, (int)training, gsum, ngroups, P, o, coef);
+  hipLaunchKernelGGL(ph_fin_b1, dim3(1), dim3(256), 0, s, need_p1, (int)training, w.gsum, ngroups, P, o, coef);
   if (need_p2) {
-    if (int rc = ph_grid(reinterpret_cast<const void*>(&ph_bwd<2>), kLds2, nchunks, "point_head_train backward pass 2", &grid)) return rc;
+    if (int rc = chunk_grid(reinterpret_cast<const void*>(&ph_bwd<2>), kLds2, kPhBlock, nchunks, "point_head_train backward pass 2", &grid)) return rc;
     hipLaunchKernelGGL((ph_bwd<2>), dim3((unsigned)grid), dim3(kPhBlock), kLds2, s, in, fold, coef, grad_logits, reinterpret_cast<float*>(part),
                        nullptr, nullptr, nullptr, o.w2 ? 1 : 0, nchunks);
-    if (int rc = ph_launch_group_sum(reinterpret_cast<const float*>(part), nchunks, kColsB2, gsum, s)) return rc;
+    if (int rc = launch_group_sum(reinterpret_cast<const float*>(part), nchunks, kColsB2, w.gsum, s, "point_head_train group sum")) return rc;
   }
-  hipLaunchKernelGGL(ph_fin_b2, dim3((kColsB2 + 255) / 256), dim3(256), 0, s, need_p2, (int)training, gsum, ngroups, P, o, coef);
+  hipLaunchKernelGGL(ph_fin_b2, dim3((kColsB2 + 255) / 256), dim3(256), 0, s, need_p2, (int)training, w.gsum, ngroups, P, o, coef);
   if (need_p3) {
-    if (int rc = ph_grid(reinterpret_cast<const void*>(&ph_bwd<3>), kLds3, nchunks, "point_head_train backward pass 3", &grid)) return rc;
+    if (int rc = chunk_grid(reinterpret_cast<const void*>(&ph_bwd<3>), kLds3, kPhBlock, nchunks, "point_head_train backward pass 3", &grid)) return rc;
     hipLaunchKernelGGL((ph_bwd<3>), dim3((unsigned)grid), dim3(kPhBlock), kLds3, s, in, fold, coef, grad_logits, reinterpret_cast<float*>(part),
                        dxa, dxb, dxc, o.w1 ? 1 : 0, nchunks);
     if (o.w1) {
-      if (int rc = ph_launch_group_sum(reinterpret_cast<const float*>(part), nchunks, kColsB3, gsum, s)) return rc;
-      hipLaunchKernelGGL(ph_fin_b3, dim3((kColsB3 + 255) / 256), dim3(256), 0, s, gsum, ngroups, o.w1);
+      if (int rc = launch_group_sum(reinterpret_cast<const float*>(part), nchunks, kColsB3, w.gsum, s, "point_head_train group sum")) return rc;
+      hipLaunchKernelGGL(ph_fin_b3, dim3((kColsB3 + 255) / 256), dim3(256), 0, s, w.gsum, ngroups, o.w1);
     }
   }
   return check_launch("point_head_train_bwd");

@@ -14,22 +14,19 @@
 // fp32-input MFMA runs at the vector rate, so the matrix pipe would buy layout, not throughput; the reductions over points
 // are what shapes these kernels.
 //
-// Reductions: no float atomics.  Points are cut into chunks of kPmChunk = 512 (a constant, not a function of the grid); a
-// chunk's partial sums are formed in a fixed lane / wave order by whichever block walks it, stored per chunk, summed per
-// group of kPmGroup chunks in chunk order in float64, and the groups summed in order in float64.  The bits of every output
+// Reductions: the fixed-order sums of csrc/chunk_sums.h over chunks of kPmChunk = 512 points; the bits of every output
 // depend on the data alone.
 //
 // Accuracy: means are taken about a shift (x: the first point; z2: the mean of the first chunk) and variances about the
 // mean (x) or the shift (z2) with the correction done in float64, so a channel with mean 1000 and spread 0.01 keeps its
 // variance.  In the chain a mean is subtracted as a float pair (hi, lo) BEFORE scaling: folding it into a bias would round
 // at the magnitude of the mean.
-#include "smos_common.h"
+#include "chunk_sums.h"
 
 namespace smos {
 namespace {
 
 constexpr int kPmChunk = 512;                // points per chunk of partial sums
-constexpr int kPmGroup = 64;                 // chunks per first-level float64 sum
 constexpr int kPmRow = 68;                   // LDS row pitch in floats (16-byte rows, 4-bank skew)
 constexpr int kPmCols2 = 64 * 64 + 64 * 8;   // backward pass 2: dW2, then M[j][0..6] and dbeta1 at [j][7]
 
@@ -45,44 +42,16 @@ enum : int {
 };
 // the float64 statistics the backward's closed forms need
 enum : int { D_MU0 = 0, D_A0 = 8, D_R0 = 16, D_COV = 24, D_R1 = 88, D_R2 = 152, D_MU1 = 216, D_END = 280 };
-// work buffer, byte offsets
-constexpr int64_t kWCoef = 0;                // 128 floats: dbeta2 / P, dgamma2 / P
-constexpr int64_t kWPart = 4096;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// sum over the groups, in group order
-__device__ __forceinline__ double total(const double* __restrict__ gsum, int64_t ngroups, int cols, int col) {
-  double s = 0.0;
-  for (int64_t g = 0; g < ngroups; ++g) s += gsum[g * cols + col];
-  return s;
-}
-
+// work buffer: the coefficients are 128 floats, dbeta2 / P and dgamma2 / P
 struct PmPoint {
   bool live;
   int64_t xoff;   // x + xoff: channel 0 of the point; channels are N apart
   int64_t yoff;   // y + yoff likewise
 };
 
-// A point past the end is clamped onto the last one (its loads are valid, its contributions are selected away).
 __device__ __forceinline__ PmPoint pm_point(int64_t p, int64_t P, int64_t N) {
-  PmPoint r;
-  r.live = p < P;
-  const int64_t pc = r.live ? p : P - 1;
-  const uint32_t s = (uint32_t)pc / (uint32_t)N;      // P < 2^31
-  const int64_t n = pc - (int64_t)s * N;
-  r.xoff = (int64_t)s * 7 * N + n;
-  r.yoff = (int64_t)s * 64 * N + n;
-  return r;
+  const ChunkPoint c = chunk_point(p, P, N);
+  return {c.live, c.s * 7 * N + c.n, c.s * 64 * N + c.n};
 }
 
 __device__ __forceinline__ void pm_load_d(const float* __restrict__ x, const float* __restrict__ fold, int64_t xoff, int64_t N,
@@ -130,15 +99,13 @@ __global__ __launch_bounds__(256) void pm_xsum(const float* __restrict__ x, int6
       }
     }
 #pragma unroll
-    for (int c = 0; c < 7; ++c) acc[c] = wave_sum_d(acc[c]);
+    for (int c = 0; c < 7; ++c) acc[c] = wave_sum(acc[c]);
     if (lane == 0) {
 #pragma unroll
       for (int c = 0; c < 7; ++c) red[wave][c] = acc[c];
       red[wave][7] = 0.0;
     }
-    __syncthreads();
-    if (tid < 8) partial[chunk * 8 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-    __syncthreads();
+    block_columns_store<8>(red, partial, chunk, tid);
   }
 }
 
@@ -170,30 +137,14 @@ __global__ __launch_bounds__(256) void pm_xcov(const float* __restrict__ x, cons
     for (int a = 0; a < 7; ++a)
 #pragma unroll
       for (int b = a; b < 7; ++b) {
-        const double s = wave_sum_d(acc[i++]);
+        const double s = wave_sum(acc[i++]);
         if (lane == 0) {
           red[wave][a * 8 + b] = s;
           red[wave][b * 8 + a] = s;
         }
       }
-    __syncthreads();
-    if (tid < 64) partial[chunk * 64 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-    __syncthreads();
+    block_columns_store<64>(red, partial, chunk, tid);
   }
-}
-
-// first-level sums: one thread per (group of kPmGroup chunks, column), chunks in order
-template <typename T>
-__global__ __launch_bounds__(256) void pm_group_sum(const T* __restrict__ partial, int64_t nchunks, int cols, double* __restrict__ gsum) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t ngroups = (nchunks + kPmGroup - 1) / kPmGroup;
-  if (i >= ngroups * cols) return;
-  const int64_t grp = i / cols;
-  const int col = (int)(i - grp * cols);
-  const int64_t c0 = grp * kPmGroup, c1 = c0 + kPmGroup < nchunks ? c0 + kPmGroup : nchunks;
-  double s = 0.0;
-  for (int64_t c = c0; c < c1; ++c) s += (double)partial[c * cols + col];
-  gsum[i] = s;
 }
 
 __global__ void pm_fin_mean0(const double* __restrict__ gsum, int64_t ngroups, const float* __restrict__ x, int64_t N, int64_t P,
@@ -208,11 +159,6 @@ struct PmParams {
   const float* w2; const float* g2; const float* b2; float* rm2; float* rv2;
   double eps[3], mom[3];
 };
-
-__device__ __forceinline__ void pm_running(float* rm, float* rv, int i, double mom, double mean, double var, int64_t P) {
-  rm[i] = (float)((1.0 - mom) * (double)rm[i] + mom * mean);
-  rv[i] = (float)((1.0 - mom) * (double)rv[i] + mom * (var * ((double)P / (double)(P - 1))));
-}
 
 // BN0 and BN1 statistics (training: from the centred second moments of x; eval: the running buffers), layer 1 folded
 __global__ __launch_bounds__(256) void pm_fin_l1(int training, const double* __restrict__ gsum, int64_t ngroups, int64_t P, PmParams q,
@@ -229,7 +175,7 @@ __global__ __launch_bounds__(256) void pm_fin_l1(int training, const double* __r
       if (training) {
         mu = dstat[D_MU0 + c];
         var = cov[c * 8 + c];
-        pm_running(q.rm0, q.rv0, c, q.mom[0], mu, var, P);
+        bn_running_update(q.rm0, q.rv0, c, q.mom[0], mu, var, P);
       } else {
         mu = (double)q.rm0[c];
         var = (double)q.rv0[c];
@@ -238,9 +184,7 @@ __global__ __launch_bounds__(256) void pm_fin_l1(int training, const double* __r
       r = 1.0 / sqrt(var + q.eps[0]);
       a = (double)q.g0[c] * r;
     }
-    const float hi = (float)mu;
-    fold[F_MU0H + c] = hi;
-    fold[F_MU0L + c] = (float)(mu - (double)hi);
+    split_hi_lo(mu, &fold[F_MU0H + c], &fold[F_MU0L + c]);
     a0[c] = a;
     dstat[D_A0 + c] = a;
     dstat[D_R0 + c] = r;
@@ -261,7 +205,7 @@ __global__ __launch_bounds__(256) void pm_fin_l1(int training, const double* __r
       for (int a = 0; a < 7; ++a)
         for (int b = 0; b < 7; ++b) var1 += u[a] * cov[a * 8 + b] * u[b];
       var1 = var1 > 0.0 ? var1 : 0.0;
-      pm_running(q.rm1, q.rv1, j, q.mom[1], mu1, var1, P);
+      bn_running_update(q.rm1, q.rv1, j, q.mom[1], mu1, var1, P);
     } else {
       mu1 = (double)q.rm1[j];
       var1 = (double)q.rv1[j];
@@ -296,19 +240,15 @@ __global__ void pm_fin_l2(int training, const double* __restrict__ gsum, int64_t
   if (j >= 64) return;
   double mu, var;
   if (training) {
-    const double s1 = total(gsum, ngroups, 128, j) / (double)P, s2 = total(gsum, ngroups, 128, 64 + j) / (double)P;
-    mu = (double)fold[F_SH2 + j] + s1;
-    var = s2 - s1 * s1;
-    var = var > 0.0 ? var : 0.0;
-    pm_running(q.rm2, q.rv2, j, q.mom[2], mu, var, P);
+    bn_stats_about_shift(gsum, ngroups, 64, j, P, &mu, &var);
+    mu += (double)fold[F_SH2 + j];
+    bn_running_update(q.rm2, q.rv2, j, q.mom[2], mu, var, P);
   } else {
     mu = (double)q.rm2[j];
     var = (double)q.rv2[j];
   }
   const double r2 = 1.0 / sqrt(var + q.eps[2]);
-  const float hi = (float)mu;
-  fold[F_MU2H + j] = hi;
-  fold[F_MU2L + j] = (float)(mu - (double)hi);
+  split_hi_lo(mu, &fold[F_MU2H + j], &fold[F_MU2L + j]);
   fold[F_G2 + j] = (float)((double)q.g2[j] * r2);
   fold[F_BET2 + j] = q.b2[j];
   fold[F_R2 + j] = (float)r2;
@@ -359,9 +299,7 @@ __global__ __launch_bounds__(256) void pm_pass(const float* __restrict__ x, cons
     if (MODE != 1) {
       red[wave][lane] = acc1;
       red[wave][64 + lane] = acc2;
-      __syncthreads();
-      if (tid < 128) partial[chunk * 128 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-      __syncthreads();
+      block_columns_store<128>(red, partial, chunk, tid);
     }
   }
 }
@@ -545,24 +483,8 @@ __global__ __launch_bounds__(256) void pm_fin_bwd2(int training, const double* _
   }
 }
 
-int64_t pm_chunks(int64_t P) { return (P + kPmChunk - 1) / kPmChunk; }
-int64_t pm_groups(int64_t P) { return (pm_chunks(P) + kPmGroup - 1) / kPmGroup; }
-int64_t pm_part_bytes(int64_t P) { return pm_chunks(P) * kPmCols2 * 4; }      // the widest partial row: pass 2 of the backward
-
-template <typename T>
-int pm_launch_group_sum(const T* partial, int64_t nchunks, int cols, double* gsum, hipStream_t s) {
-  const int64_t items = ((nchunks + kPmGroup - 1) / kPmGroup) * cols;
-  hipLaunchKernelGGL((pm_group_sum<T>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, partial, nchunks, cols, gsum);
-  return check_launch("point_mlp group sum");
-}
-
-int pm_grid(const void* fn, int block, int64_t nchunks, const char* what, int64_t* grid) {
-  KernelSetup ks;
-  if (int rc = kernel_setup(fn, 0, block, &ks, what)) return rc;
-  const int64_t resident = conv_grid_cap((int64_t)(ks.per_cu > 0 ? ks.per_cu : 1) * (ks.cus > 0 ? ks.cus : 1));   // (the test hook's cap: several chunks per block)
-  *grid = nchunks < resident ? nchunks : resident;
-  return SMOS_OK;
-}
+// the widest partial row is pass 2 of the backward
+ChunkWork pm_work(void* work, int64_t P) { return chunk_work(work, P, kPmChunk, kPmCols2); }
 
 int pm_params(const void* const* p, const double* eps_mom, PmParams* q) {
   for (int i = 0; i < 14; ++i) SMOS_REQUIRE(p[i], "point_mlp: null parameter pointer %d", i);
@@ -586,8 +508,7 @@ extern "C" int32_t smos_point_mlp_fold_floats(void) { return F_END; }
 extern "C" int32_t smos_point_mlp_stat_doubles(void) { return D_END; }
 
 extern "C" int64_t smos_point_mlp_work_bytes(int64_t P) {
-  if (P < 1 || P >= (1LL << 31) - kPmChunk) return -1;
-  return kWPart + pm_part_bytes(P) + pm_groups(P) * kPmCols2 * 8;
+  return pm_work(nullptr, P).bytes;
 }
 
 extern "C" int smos_point_mlp_fwd(const float* x, int64_t S, int64_t N, int32_t training, const void* const* params,
@@ -596,37 +517,35 @@ extern "C" int smos_point_mlp_fwd(const float* x, int64_t S, int64_t N, int32_t 
   SMOS_REQUIRE(x && params && eps_mom && y && fold && dstat && work, "point_mlp_fwd: null pointer");
   SMOS_REQUIRE(S > 0 && N > 0, "point_mlp_fwd: bad sizes");
   const int64_t P = S * N;
-  const int64_t need = smos_point_mlp_work_bytes(P);
-  SMOS_REQUIRE(need > 0 && work_bytes >= need, "point_mlp_fwd: %lld points need %lld bytes of work space, got %lld", (long long)P,
-               (long long)need, (long long)work_bytes);
+  const ChunkWork w = pm_work(work, P);
+  if (int rc = chunk_work_check(w, P, work_bytes, "point_mlp_fwd")) return rc;
   SMOS_REQUIRE(!training || P > 1, "point_mlp_fwd: batch statistics need more than one point");
   PmParams q;
   if (int rc = pm_params(params, eps_mom, &q)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t nchunks = pm_chunks(P), ngroups = pm_groups(P);
-  double* partial = reinterpret_cast<double*>(static_cast<char*>(work) + kWPart);
-  double* gsum = reinterpret_cast<double*>(static_cast<char*>(work) + kWPart + pm_part_bytes(P));
+  const int64_t nchunks = w.nchunks, ngroups = w.ngroups;
+  double* partial = reinterpret_cast<double*>(w.part);
   int64_t grid = 1;
   if (training) {
-    if (int rc = pm_grid(reinterpret_cast<const void*>(&pm_xsum), 256, nchunks, "point_mlp x sums", &grid)) return rc;
+    if (int rc = chunk_grid(reinterpret_cast<const void*>(&pm_xsum), 0, 256, nchunks, "point_mlp x sums", &grid)) return rc;
     hipLaunchKernelGGL(pm_xsum, dim3((unsigned)grid), dim3(256), 0, s, x, P, N, nchunks, partial);
-    if (int rc = pm_launch_group_sum(partial, nchunks, 8, gsum, s)) return rc;
-    hipLaunchKernelGGL(pm_fin_mean0, dim3(1), dim3(64), 0, s, gsum, ngroups, x, N, P, dstat);
-    if (int rc = pm_grid(reinterpret_cast<const void*>(&pm_xcov), 256, nchunks, "point_mlp x moments", &grid)) return rc;
+    if (int rc = launch_group_sum(partial, nchunks, 8, w.gsum, s, "point_mlp group sum")) return rc;
+    hipLaunchKernelGGL(pm_fin_mean0, dim3(1), dim3(64), 0, s, w.gsum, ngroups, x, N, P, dstat);
+    if (int rc = chunk_grid(reinterpret_cast<const void*>(&pm_xcov), 0, 256, nchunks, "point_mlp x moments", &grid)) return rc;
     hipLaunchKernelGGL(pm_xcov, dim3((unsigned)grid), dim3(256), 0, s, x, dstat, P, N, nchunks, partial);
-    if (int rc = pm_launch_group_sum(partial, nchunks, 64, gsum, s)) return rc;
+    if (int rc = launch_group_sum(partial, nchunks, 64, w.gsum, s, "point_mlp group sum")) return rc;
   }
-  hipLaunchKernelGGL(pm_fin_l1, dim3(1), dim3(256), 0, s, (int)training, gsum, ngroups, P, q, fold, dstat);
+  hipLaunchKernelGGL(pm_fin_l1, dim3(1), dim3(256), 0, s, (int)training, w.gsum, ngroups, P, q, fold, dstat);
   if (training) {
-    if (int rc = pm_grid(reinterpret_cast<const void*>(&pm_pass<0>), 256, nchunks, "point_mlp z2 sums", &grid)) return rc;
+    if (int rc = chunk_grid(reinterpret_cast<const void*>(&pm_pass<0>), 0, 256, nchunks, "point_mlp z2 sums", &grid)) return rc;
     // the shift: the mean of z2 over the first chunk
     hipLaunchKernelGGL((pm_pass<0>), dim3(1), dim3(256), 0, s, x, fold, nullptr, nullptr, partial, P, N, (int64_t)1);
     hipLaunchKernelGGL(pm_fin_shift, dim3(1), dim3(64), 0, s, partial, P < kPmChunk ? P : (int64_t)kPmChunk, fold);
     hipLaunchKernelGGL((pm_pass<0>), dim3((unsigned)grid), dim3(256), 0, s, x, fold, nullptr, nullptr, partial, P, N, nchunks);
-    if (int rc = pm_launch_group_sum(partial, nchunks, 128, gsum, s)) return rc;
+    if (int rc = launch_group_sum(partial, nchunks, 128, w.gsum, s, "point_mlp group sum")) return rc;
   }
-  hipLaunchKernelGGL(pm_fin_l2, dim3(1), dim3(64), 0, s, (int)training, gsum, ngroups, P, q, fold, dstat);
-  if (int rc = pm_grid(reinterpret_cast<const void*>(&pm_pass<1>), 256, nchunks, "point_mlp y", &grid)) return rc;
+  hipLaunchKernelGGL(pm_fin_l2, dim3(1), dim3(64), 0, s, (int)training, w.gsum, ngroups, P, q, fold, dstat);
+  if (int rc = chunk_grid(reinterpret_cast<const void*>(&pm_pass<1>), 0, 256, nchunks, "point_mlp y", &grid)) return rc;
   hipLaunchKernelGGL((pm_pass<1>), dim3((unsigned)grid), dim3(256), 0, s, x, fold, nullptr, y, nullptr, P, N, nchunks);
   return check_launch("point_mlp_fwd");
 }
@@ -637,9 +556,8 @@ extern "C" int smos_point_mlp_bwd(const float* x, const float* grad_y, int64_t S
   SMOS_REQUIRE(x && grad_y && params && eps_mom && fold && dstat && grads && work, "point_mlp_bwd: null pointer");
   SMOS_REQUIRE(S > 0 && N > 0, "point_mlp_bwd: bad sizes");
   const int64_t P = S * N;
-  const int64_t need = smos_point_mlp_work_bytes(P);
-  SMOS_REQUIRE(need > 0 && work_bytes >= need, "point_mlp_bwd: %lld points need %lld bytes of work space, got %lld", (long long)P,
-               (long long)need, (long long)work_bytes);
+  const ChunkWork w = pm_work(work, P);
+  if (int rc = chunk_work_check(w, P, work_bytes, "point_mlp_bwd")) return rc;
   PmParams q;
   if (int rc = pm_params(params, eps_mom, &q)) return rc;
   // grads: gamma0, beta0, W1, gamma1, beta1, W2, gamma2, beta2 (NULL: not wanted)
@@ -652,24 +570,23 @@ extern "C" int smos_point_mlp_bwd(const float* x, const float* grad_y, int64_t S
   const int need_p2 = need_low || need_w2, need_p1 = (d_g2 || d_b2 || (training && need_p2)) ? 1 : 0;
   if (!need_p1 && !need_p2) return SMOS_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int64_t nchunks = pm_chunks(P), ngroups = pm_groups(P);
-  float* coef = reinterpret_cast<float*>(static_cast<char*>(work) + kWCoef);
-  char* part = static_cast<char*>(work) + kWPart;
-  double* gsum = reinterpret_cast<double*>(part + pm_part_bytes(P));
+  const int64_t nchunks = w.nchunks, ngroups = w.ngroups;
+  float* coef = static_cast<float*>(w.coef);
+  char* part = w.part;
   int64_t grid = 1;
   if (need_p1) {
-    if (int rc = pm_grid(reinterpret_cast<const void*>(&pm_pass<2>), 256, nchunks, "point_mlp backward pass 1", &grid)) return rc;
+    if (int rc = chunk_grid(reinterpret_cast<const void*>(&pm_pass<2>), 0, 256, nchunks, "point_mlp backward pass 1", &grid)) return rc;
     hipLaunchKernelGGL((pm_pass<2>), dim3((unsigned)grid), dim3(256), 0, s, x, fold, grad_y, nullptr, reinterpret_cast<double*>(part), P, N,
                        nchunks);
-    if (int rc = pm_launch_group_sum(reinterpret_cast<const double*>(part), nchunks, 128, gsum, s)) return rc;
+    if (int rc = launch_group_sum(reinterpret_cast<const double*>(part), nchunks, 128, w.gsum, s, "point_mlp group sum")) return rc;
   }
-  hipLaunchKernelGGL(pm_fin_bwd1, dim3(1), dim3(64), 0, s, need_p1, (int)training, gsum, ngroups, P, d_g2, d_b2, coef);
+  hipLaunchKernelGGL(pm_fin_bwd1, dim3(1), dim3(64), 0, s, need_p1, (int)training, w.gsum, ngroups, P, d_g2, d_b2, coef);
   if (need_p2) {
-    if (int rc = pm_grid(reinterpret_cast<const void*>(&pm_bwd2), 64, nchunks, "point_mlp backward pass 2", &grid)) return rc;
+    if (int rc = chunk_grid(reinterpret_cast<const void*>(&pm_bwd2), 0, 64, nchunks, "point_mlp backward pass 2", &grid)) return rc;
     hipLaunchKernelGGL(pm_bwd2, dim3((unsigned)grid), dim3(64), 0, s, x, fold, coef, grad_y, P, N, nchunks, reinterpret_cast<float*>(part),
                        need_w2, need_low);
-    if (int rc = pm_launch_group_sum(reinterpret_cast<const float*>(part), nchunks, kPmCols2, gsum, s)) return rc;
-    hipLaunchKernelGGL(pm_fin_bwd2, dim3(1), dim3(256), 0, s, (int)training, gsum, ngroups, q, dstat, o, need_low);
+    if (int rc = launch_group_sum(reinterpret_cast<const float*>(part), nchunks, kPmCols2, w.gsum, s, "point_mlp group sum")) return rc;
+    hipLaunchKernelGGL(pm_fin_bwd2, dim3(1), dim3(256), 0, s, (int)training, w.gsum, ngroups, q, dstat, o, need_low);
   }
   return check_launch("point_mlp_bwd");
 }

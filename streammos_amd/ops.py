@@ -322,8 +322,58 @@ def point_mlp_chunk():
     return _lib.query("smos_point_mlp_chunk")
 
 
-def _point_mlp_ptrs(tensors):
+# ---- what the two fused training ops (point_mlp_train, point_head_train) share; ``op`` is the prefix of their messages ----
+def _ptr_array(tensors):
     return (_lib.vp * len(tensors))(*[_ptr(t) for t in tensors])
+
+
+def _train_work(tag, query, points, dev):
+    """(work buffer from the scratch registry, its bytes) for ``points`` points; (None, need <= 0) past the kernels' range."""
+    need = _lib.query(query, points)
+    return (shared.get(tag, (need,), torch.uint8, dev) if need > 0 else None), need
+
+
+def _train_fold_dstat(abi, dev):
+    """The folded block and the float64 statistics a forward leaves for its backward, sized by ``abi``'s two queries."""
+    return (torch.empty(_lib.query(abi + "_fold_floats"), dtype=torch.float32, device=dev),
+            torch.empty(_lib.query(abi + "_stat_doubles"), dtype=torch.float64, device=dev))
+
+
+def _train_check_bns(op, pairs, first):
+    for i, (bn, c) in enumerate(pairs, first):
+        if bn.weight is None or bn.bias is None or bn.running_mean is None or bn.running_var is None or bn.momentum is None:
+            raise RuntimeError("%s: bn%d must be affine, track running statistics and have a momentum" % (op, i))
+        if bn.weight.numel() != c:
+            raise RuntimeError("%s: bn%d has %d channels, want %d" % (op, i, bn.weight.numel(), c))
+
+
+def _train_conv1x1(op, name, m, shape, rule, bias=False, allow_tensor=False):
+    """The weight of the 1x1 convolution ``m`` [cout, cin(,1,1)] with or without a bias; ``rule`` ends the bias message."""
+    is_module = isinstance(m, torch.nn.Module)
+    if not is_module and not allow_tensor:
+        raise RuntimeError("%s: %s must be the convolution module" % (op, name))
+    if is_module and (getattr(m, "bias", None) is not None) != bias:
+        raise RuntimeError("%s: %s %s a bias; %s" % (op, name, "lacks" if bias else "has", rule))
+    w = m.weight if is_module else m
+    if tuple(w.shape[:2]) != shape or w.numel() != shape[0] * shape[1]:
+        raise RuntimeError("%s: %s is %s, want a 1x1 convolution %d -> %d" % (op, name, tuple(w.shape), shape[1], shape[0]))
+    return w
+
+
+def _train_check_tensors(op, tensors, dev):
+    for t in tensors:
+        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("%s: parameters and buffers must be contiguous float32 tensors on %s" % (op, dev))
+
+
+def _bn_eps_mom(bns):
+    return tuple(float(bn.eps) for bn in bns) + tuple(float(bn.momentum) for bn in bns)
+
+
+def _bn_count_batch(bns):
+    for bn in bns:
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
 
 
 class _PointMlpTrain(torch.autograd.Function):
@@ -334,17 +384,15 @@ class _PointMlpTrain(torch.autograd.Function):
     def forward(ctx, x, g0, b0, w1, g1, b1, w2, g2, b2, buffers, eps_mom, training):
         s, _, n = x.shape[:3]
         dev = x.device
-        need = _lib.query("smos_point_mlp_work_bytes", s * n)
+        work, need = _train_work("point_mlp", "smos_point_mlp_work_bytes", s * n, dev)
         if need <= 0:
             raise RuntimeError("point_mlp_train: %d x %d points is more than the kernels are set up for" % (s, n))
-        work = shared.get("point_mlp", (need,), torch.uint8, dev)
         y = torch.empty((s, 64, n, 1), dtype=torch.float32, device=dev)
-        fold = torch.empty(_lib.query("smos_point_mlp_fold_floats"), dtype=torch.float32, device=dev)
-        dstat = torch.empty(_lib.query("smos_point_mlp_stat_doubles"), dtype=torch.float64, device=dev)
+        fold, dstat = _train_fold_dstat("smos_point_mlp", dev)
         rm0, rv0, rm1, rv1, rm2, rv2 = buffers
         params = (g0, b0, rm0, rv0, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2)
         with _on(dev), profiling.span_f("point_mlp_%s[%dx%d]", ("train" if training else "eval", s, n)):
-            _lib.call("smos_point_mlp_fwd", x.data_ptr(), s, n, int(training), _point_mlp_ptrs(params), _lib.f64_array(eps_mom),
+            _lib.call("smos_point_mlp_fwd", x.data_ptr(), s, n, int(training), _ptr_array(params), _lib.f64_array(eps_mom),
                       y.data_ptr(), fold.data_ptr(), dstat.data_ptr(), work.data_ptr(), need, _stream(x))
         ctx.save_for_backward(x, g0, b0, w1, g1, b1, w2, g2, b2, fold, dstat)
         ctx.buffers, ctx.eps_mom, ctx.training = buffers, eps_mom, bool(training)
@@ -361,22 +409,12 @@ class _PointMlpTrain(torch.autograd.Function):
         params = (g0, b0, rm0, rv0, w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2)
         grads = [torch.empty_like(p) if ctx.needs_input_grad[1 + i] else None for i, p in enumerate((g0, b0, w1, g1, b1, w2, g2, b2))]
         if any(g is not None for g in grads):
-            need = _lib.query("smos_point_mlp_work_bytes", s * n)
-            work = shared.get("point_mlp", (need,), torch.uint8, dev)
+            work, need = _train_work("point_mlp", "smos_point_mlp_work_bytes", s * n, dev)
             with _on(dev), profiling.span_f("point_mlp_bwd[%dx%d]", (s, n)):
-                _lib.call("smos_point_mlp_bwd", x.data_ptr(), gy.data_ptr(), s, n, int(ctx.training), _point_mlp_ptrs(params),
-                          _lib.f64_array(ctx.eps_mom), fold.data_ptr(), dstat.data_ptr(), _point_mlp_ptrs(grads), work.data_ptr(),
+                _lib.call("smos_point_mlp_bwd", x.data_ptr(), gy.data_ptr(), s, n, int(ctx.training), _ptr_array(params),
+                          _lib.f64_array(ctx.eps_mom), fold.data_ptr(), dstat.data_ptr(), _ptr_array(grads), work.data_ptr(),
                           need, _stream(x))
         return (None, *grads, None, None, None)
-
-
-def _point_mlp_weight(name, m, shape):
-    w = m.weight if isinstance(m, torch.nn.Module) else m
-    if isinstance(m, torch.nn.Module) and getattr(m, "bias", None) is not None:
-        raise RuntimeError("point_mlp_train: %s has a bias; the point MLP's convolutions have none" % name)
-    if tuple(w.shape[:2]) != shape or w.numel() != shape[0] * shape[1]:
-        raise RuntimeError("point_mlp_train: %s is %s, want a 1x1 convolution %d -> %d" % (name, tuple(w.shape), shape[1], shape[0]))
-    return w
 
 
 def point_mlp_train(x, bn0, conv1, bn1, conv2, bn2, training=None):
@@ -398,26 +436,18 @@ def point_mlp_train(x, bn0, conv1, bn1, conv2, bn2, training=None):
         raise RuntimeError("point_mlp_train: x is %s, want [S,7,N(,1)] with S*N > 0" % (tuple(x.shape),))
     training = bool(bn0.training if training is None else training)
     bns = (bn0, bn1, bn2)
-    for i, (bn, c) in enumerate(zip(bns, (7, 64, 64))):
-        if bn.weight is None or bn.bias is None or bn.running_mean is None or bn.running_var is None or bn.momentum is None:
-            raise RuntimeError("point_mlp_train: bn%d must be affine, track running statistics and have a momentum" % i)
-        if bn.weight.numel() != c:
-            raise RuntimeError("point_mlp_train: bn%d has %d channels, want %d" % (i, bn.weight.numel(), c))
-    w1 = _point_mlp_weight("conv1", conv1, (64, 7))
-    w2 = _point_mlp_weight("conv2", conv2, (64, 64))
+    _train_check_bns("point_mlp_train", zip(bns, (7, 64, 64)), 0)
+    rule = "the point MLP's convolutions have none"
+    w1 = _train_conv1x1("point_mlp_train", "conv1", conv1, (64, 7), rule, allow_tensor=True)
+    w2 = _train_conv1x1("point_mlp_train", "conv2", conv2, (64, 64), rule, allow_tensor=True)
     tensors = [bn0.weight, bn0.bias, w1, bn1.weight, bn1.bias, w2, bn2.weight, bn2.bias]
     buffers = tuple(b for bn in bns for b in (bn.running_mean, bn.running_var))
-    for t in tensors + list(buffers):
-        if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("point_mlp_train: parameters and buffers must be contiguous float32 tensors on %s" % x.device)
+    _train_check_tensors("point_mlp_train", tensors + list(buffers), x.device)
     if training and x.shape[0] * x.shape[2] < 2:
         raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (x.shape,))
-    eps_mom = tuple(float(bn.eps) for bn in bns) + tuple(float(bn.momentum) for bn in bns)
-    y = _PointMlpTrain.apply(x.detach().contiguous(), *tensors, buffers, eps_mom, training)
+    y = _PointMlpTrain.apply(x.detach().contiguous(), *tensors, buffers, _bn_eps_mom(bns), training)
     if training:
-        for bn in bns:
-            if bn.num_batches_tracked is not None:
-                bn.num_batches_tracked.add_(1)
+        _bn_count_batch(bns)
     return y
 
 
@@ -445,17 +475,15 @@ class _PointHeadTrain(torch.autograd.Function):
     def forward(ctx, a, b, c, w1, g1, b1, w2, g2, b2, w3, bias3, buffers, eps_mom, training, masks, scale):
         bs, _, n = a.shape[:3]
         dev = a.device
-        need = _lib.query("smos_point_head_train_work_bytes", bs * n)
-        work = shared.get("point_head_train", (need,), torch.uint8, dev)
+        work, need = _train_work("point_head_train", "smos_point_head_train_work_bytes", bs * n, dev)
         logits = torch.empty((bs, 3, n, 1), dtype=torch.float32, device=dev)
-        fold = torch.empty(_lib.query("smos_point_head_train_fold_floats"), dtype=torch.float32, device=dev)
-        dstat = torch.empty(_lib.query("smos_point_head_train_stat_doubles"), dtype=torch.float64, device=dev)
+        fold, dstat = _train_fold_dstat("smos_point_head_train", dev)
         rm1, rv1, rm2, rv2 = buffers
         params = (w1, g1, b1, rm1, rv1, w2, g2, b2, rm2, rv2, w3, bias3)
         pitch = _lib.i64_array([_point_head_pitch(t) for t in (a, b, c)])
         with _on(dev), profiling.span_f("point_head_%s[%dx%d]", ("train" if training else "eval", bs, n)):
             _lib.call("smos_point_head_train_fwd", a.data_ptr(), b.data_ptr(), c.data_ptr(), pitch, _ptr(masks), scale, bs, n,
-                      int(training), _point_mlp_ptrs(params), _lib.f64_array(eps_mom), logits.data_ptr(), fold.data_ptr(),
+                      int(training), _ptr_array(params), _lib.f64_array(eps_mom), logits.data_ptr(), fold.data_ptr(),
                       dstat.data_ptr(), work.data_ptr(), need, _stream(a))
         ctx.save_for_backward(a, b, c, fold, masks)
         ctx.param_like = (w1, g1, b1, w2, g2, b2, w3, bias3)
@@ -473,27 +501,14 @@ class _PointHeadTrain(torch.autograd.Function):
         dx = [torch.empty((bs, 64, n, 1), dtype=torch.float32, device=dev) for _ in range(3)] if want_x else [None] * 3
         dp = [torch.empty_like(p) if ctx.needs_input_grad[3 + i] else None for i, p in enumerate(ctx.param_like)]
         if want_x or any(g is not None for g in dp):
-            need = _lib.query("smos_point_head_train_work_bytes", bs * n)
-            work = shared.get("point_head_train", (need,), torch.uint8, dev)
+            work, need = _train_work("point_head_train", "smos_point_head_train_work_bytes", bs * n, dev)
             pitch = _lib.i64_array([_point_head_pitch(t) for t in (a, b, c)])
             with _on(dev), profiling.span_f("point_head_bwd[%dx%d]", (bs, n)):
                 _lib.call("smos_point_head_train_bwd", a.data_ptr(), b.data_ptr(), c.data_ptr(), pitch, _ptr(masks), ctx.scale,
-                          gl.data_ptr(), bs, n, int(ctx.training), fold.data_ptr(), _point_mlp_ptrs(dx + dp), work.data_ptr(),
+                          gl.data_ptr(), bs, n, int(ctx.training), fold.data_ptr(), _ptr_array(dx + dp), work.data_ptr(),
                           need, _stream(a))
         dx = [g if ctx.needs_input_grad[i] else None for i, g in enumerate(dx)]
         return (*dx, *dp, None, None, None, None, None)
-
-
-def _point_head_conv(name, m, shape, bias):
-    if not isinstance(m, torch.nn.Module):
-        raise RuntimeError("point_head_train: %s must be the convolution module" % name)
-    if (m.bias is not None) != bias:
-        raise RuntimeError("point_head_train: %s %s a bias; conv1 and conv2 have none, conv3 has one"
-                           % (name, "lacks" if bias else "has"))
-    w = m.weight
-    if tuple(w.shape[:2]) != shape or w.numel() != shape[0] * shape[1]:
-        raise RuntimeError("point_head_train: %s is %s, want a 1x1 convolution %d -> %d" % (name, tuple(w.shape), shape[1], shape[0]))
-    return w
 
 
 def point_head_train(a, b, c, conv1, bn1, conv2, bn2, conv3, p=0.2, training=None, keep=None):
@@ -527,19 +542,15 @@ def point_head_train(a, b, c, conv1, bn1, conv2, bn2, conv3, p=0.2, training=Non
     bs, _, n = xs[0].shape[:3]
     dev = xs[0].device
     training = bool(bn1.training if training is None else training)
-    for i, (bn, ch) in enumerate(((bn1, 96), (bn2, 64)), 1):
-        if bn.weight is None or bn.bias is None or bn.running_mean is None or bn.running_var is None or bn.momentum is None:
-            raise RuntimeError("point_head_train: bn%d must be affine, track running statistics and have a momentum" % i)
-        if bn.weight.numel() != ch:
-            raise RuntimeError("point_head_train: bn%d has %d channels, want %d" % (i, bn.weight.numel(), ch))
-    w1 = _point_head_conv("conv1", conv1, (96, 192), False)
-    w2 = _point_head_conv("conv2", conv2, (64, 96), False)
-    w3 = _point_head_conv("conv3", conv3, (3, 64), True)
+    bns = (bn1, bn2)
+    _train_check_bns("point_head_train", zip(bns, (96, 64)), 1)
+    rule = "conv1 and conv2 have none, conv3 has one"
+    w1 = _train_conv1x1("point_head_train", "conv1", conv1, (96, 192), rule)
+    w2 = _train_conv1x1("point_head_train", "conv2", conv2, (64, 96), rule)
+    w3 = _train_conv1x1("point_head_train", "conv3", conv3, (3, 64), rule, bias=True)
     tensors = [w1, bn1.weight, bn1.bias, w2, bn2.weight, bn2.bias, w3, conv3.bias]
     buffers = (bn1.running_mean, bn1.running_var, bn2.running_mean, bn2.running_var)
-    for t in tensors + list(buffers):
-        if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("point_head_train: parameters and buffers must be contiguous float32 tensors on %s" % dev)
+    _train_check_tensors("point_head_train", tensors + list(buffers), dev)
     if _lib.query("smos_point_head_train_work_bytes", bs * n) <= 0:
         raise RuntimeError("point_head_train: %d x %d points is more than the kernels are set up for" % (bs, n))
     if training and bs * n < 2:
@@ -563,14 +574,11 @@ def point_head_train(a, b, c, conv1, bn1, conv2, bn2, conv3, p=0.2, training=Non
             _lib.call("smos_point_head_train_masks", _ptr(k1), _ptr(k2), _ptr(seed), bs, n, masks.data_ptr(), _stream(xs[0]))
     elif keep is not None and training:
         raise RuntimeError("point_head_train: keep masks given with p = 0")
-    eps_mom = (float(bn1.eps), float(bn2.eps), float(bn1.momentum), float(bn2.momentum))
     need_grad = torch.is_grad_enabled()
     xin = [x if need_grad and x.requires_grad else x.detach() for x in xs]
-    out = _PointHeadTrain.apply(*xin, *tensors, buffers, eps_mom, training, masks, 1.0 / (1.0 - p))
+    out = _PointHeadTrain.apply(*xin, *tensors, buffers, _bn_eps_mom(bns), training, masks, 1.0 / (1.0 - p))
     if training:
-        for bn in (bn1, bn2):
-            if bn.num_batches_tracked is not None:
-                bn.num_batches_tracked.add_(1)
+        _bn_count_batch(bns)
     out._smos_point_head = (masks, seed, bs, n)
     return out
 

@@ -93,6 +93,27 @@ class PointNet(nn.Module):
         return self.layer(x)
 
 
+def _is_conv1x1(conv, cin, cout, bias, device):
+    """A plain float32 1x1 ``nn.Conv2d`` cin -> cout on ``device``, with a bias or without as ``bias`` says."""
+    return (type(conv) is nn.Conv2d and conv.in_channels == cin and conv.out_channels == cout and (conv.bias is not None) == bias
+            and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
+            and conv.weight.dtype == torch.float32 and conv.weight.device == device)
+
+
+def _bn_single_process(bn, channels, training, device):
+    """A float32 ``nn.BatchNorm2d`` -- or an ``nn.SyncBatchNorm`` whose process group is one process -- over ``channels`` on
+    ``device``: affine, with running statistics and a momentum, in the mode ``training``."""
+    if type(bn) is nn.SyncBatchNorm:
+        dist = torch.distributed
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(bn.process_group) > 1:
+            return False
+    elif type(bn) is not nn.BatchNorm2d:
+        return False
+    return (bn.num_features == channels and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and bn.running_mean is not None and bn.training == training
+            and bn.weight.dtype == torch.float32 and bn.weight.device == device)
+
+
 class PointNetStacker(nn.Module):
     """networks/backbone.py:233-250."""
 
@@ -126,22 +147,10 @@ class PointNetStacker(nn.Module):
         bn0, conv1, bn1, conv2, bn2 = a[0], a[1], a[2], b[0], b[1]
         if not all(type(m) is nn.ReLU for m in (a[3], b[2])):
             return None
-        for conv, cin in ((conv1, 7), (conv2, 64)):
-            if not (type(conv) is nn.Conv2d and conv.in_channels == cin and conv.out_channels == 64 and conv.bias is None
-                    and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
-                    and conv.weight.dtype == torch.float32 and conv.weight.device == x.device):
-                return None
-        for bn, c in ((bn0, 7), (bn1, 64), (bn2, 64)):
-            if type(bn) is nn.SyncBatchNorm:
-                dist = torch.distributed
-                if dist.is_available() and dist.is_initialized() and dist.get_world_size(bn.process_group) > 1:
-                    return None
-            elif type(bn) is not nn.BatchNorm2d:
-                return None
-            if not (bn.num_features == c and bn.affine and bn.track_running_stats and bn.momentum is not None
-                    and bn.running_mean is not None and bn.training == self.training
-                    and bn.weight.dtype == torch.float32 and bn.weight.device == x.device):
-                return None
+        if not all(_is_conv1x1(conv, cin, 64, False, x.device) for conv, cin in ((conv1, 7), (conv2, 64))):
+            return None
+        if not all(_bn_single_process(bn, c, self.training, x.device) for bn, c in ((bn0, 7), (bn1, 64), (bn2, 64))):
+            return None
         return bn0, conv1, bn1, conv2, bn2
 
     def forward(self, x):
@@ -189,23 +198,11 @@ def _point_head_modules(fusion, pred, xs):
         return None
     conv1, bn1, conv2, bn2, conv3 = merge[0], merge[1], merge[3], merge[4], head[0]
     dev = xs[0].device
-    for conv, cin, cout, bias in ((conv1, 192, 96, False), (conv2, 96, 64, False), (conv3, 64, 3, True)):
-        if not (type(conv) is nn.Conv2d and conv.in_channels == cin and conv.out_channels == cout
-                and (conv.bias is not None) == bias and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
-                and conv.padding == (0, 0) and conv.groups == 1 and conv.weight.dtype == torch.float32
-                and conv.weight.device == dev):
-            return None
-    for bn, c in ((bn1, 96), (bn2, 64)):
-        if type(bn) is nn.SyncBatchNorm:
-            dist = torch.distributed
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size(bn.process_group) > 1:
-                return None
-        elif type(bn) is not nn.BatchNorm2d:
-            return None
-        if not (bn.num_features == c and bn.affine and bn.track_running_stats and bn.momentum is not None
-                and bn.running_mean is not None and bn.training == fusion.training
-                and bn.weight.dtype == torch.float32 and bn.weight.device == dev):
-            return None
+    if not all(_is_conv1x1(conv, cin, cout, bias, dev)
+               for conv, cin, cout, bias in ((conv1, 192, 96, False), (conv2, 96, 64, False), (conv3, 64, 3, True))):
+        return None
+    if not all(_bn_single_process(bn, c, fusion.training, dev) for bn, c in ((bn1, 96), (bn2, 64))):
+        return None
     if not fusion.training:
         params = [conv1.weight, bn1.weight, bn1.bias, conv2.weight, bn2.weight, bn2.bias, conv3.weight, conv3.bias]
         if not (torch.is_grad_enabled() and any(t.requires_grad for t in list(xs) + params)):

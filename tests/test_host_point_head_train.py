@@ -201,6 +201,12 @@ def test_queries_and_the_python_refusals():
     assert [lib.smos_point_head_train_mask_words(p) for p in (1, 7, 4 * 130000)] == [8, 56, 8 * 4 * 130000]      # 32 bytes a point
     for q in (lib.smos_point_head_train_work_bytes, lib.smos_point_head_train_mask_words):
         assert q(0) == -1 and q(1 << 31) == -1
+        assert q((1 << 31) - chunk) == -1 and q((1 << 31) - chunk - 1) > 0
+    # pinned: 4096 + chunks * row * 4 + groups * row * 8 with rows of 18432 floats, groups of 64 chunks
+    pins = {1: 225280, 1024: 225280, 1025: 299008, 65537: 5091328, 520000: 38637568}
+    assert {p: lib.smos_point_head_train_work_bytes(p) for p in pins} == pins
+    assert (lib.smos_point_head_train_fold_floats(), lib.smos_point_head_train_stat_doubles()) == (25828, 320)
+    assert all(lib.smos_point_head_train_mask_words(p) == 8 * p for p in pins)
     c = cases.make_case("plain", 1, 2)
     fusion, pred = cases.build_modules(c, torch.float32)
     m, head = fusion.merge_layer, pred.pred_layer[0]

@@ -120,6 +120,11 @@ def test_work_space_query_and_the_python_refusals():
     assert all(s > 0 and s % 8 == 0 for s in sizes) and sizes[0] == sizes[1] < sizes[2] < sizes[3]
     assert sizes[3] < 80 << 20                                   # the training shape: tens of MB, not an activation
     assert lib.smos_point_mlp_work_bytes(0) == -1 and lib.smos_point_mlp_work_bytes(1 << 31) == -1
+    # pinned: 4096 + chunks * row * 4 + groups * row * 8 with rows of 4608 floats, groups of 64 chunks
+    pins = {1: 59392, 512: 59392, 513: 77824, 32769: 1275904, 1560000: 57935872, 0: -1, (1 << 31) - chunk: -1}
+    assert {p: lib.smos_point_mlp_work_bytes(p) for p in pins} == pins
+    assert lib.smos_point_mlp_work_bytes((1 << 31) - chunk - 1) > 0
+    assert (lib.smos_point_mlp_fold_floats(), lib.smos_point_mlp_stat_doubles()) == (9296, 280)
     m = cases.build_modules(cases.make_case("normal", 1, 5), torch.float32)
     a, b = m.layer[0].layer, m.layer[1].layer
     with pytest.raises(RuntimeError, match="GPU memory"):
