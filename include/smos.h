@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define SMOS_ABI_VERSION 3
+#define SMOS_ABI_VERSION 4
 
 enum smos_status {
   SMOS_OK = 0,
@@ -41,7 +41,7 @@ int smos_abi_version(void);
 const char* smos_last_error(void);
 /* Test hook (process-wide, not part of the data path; the one piece of state the library keeps): caps the grid of the
  * persistent convolution kernels (smos_conv_cl / _rows_cl / _wino_cl / _wino1d_cl / _bf16_cl), of smos_stem_gemm, of
- * smos_pointnet_scatter / _rows, of smos_gather_scatter_cl, of smos_point_head / _gather, of smos_tta_argmax and of the emit, copy, start and sum
+ * smos_pointnet_scatter / _rows, of smos_gather_scatter_cl, of the three smos_gather_scatter_train_* entries, of smos_point_head / _gather, of smos_tta_argmax and of the emit, copy, start and sum
  * kernels of smos_bilinear_gather_bwd_det / smos_msda_bwd_det and of smos_train_prep_build / _draws and smos_copy_paste_* at `blocks`, 0 = no cap.  It makes one block walk several work items -- the
  * item-boundary code paths, a wave's whole-tile / head / tail units of the stem, the scatter's software pipeline -- on shapes
  * small enough to check against float64.  The results do not depend on it. */
@@ -120,6 +120,50 @@ int smos_bilinear_gather_bwd_det(const float* grad_out, const int64_t* grad_out_
                                  float* grad_grid, const int64_t* grad_grid_stride, int64_t B, int64_t C, int64_t H,
                                  int64_t W, int64_t N, const float* scale, void* work, int64_t work_bytes,
                                  smos_stream_t stream);
+
+/* --------------------------------------------------------------------------------------------
+ * Training form of a cross-view transfer: smos_bilinear_gather_fwd followed by smos_voxel_maxpool_fwd (D = 2) without the
+ * [B, C, N] tensor between them, and the gradient of the pair with respect to grid (csrc/gather_scatter_train.hip).  Float32.
+ *   grid    [B, C, Hg, Wg]  element strides grid_stride[4]
+ *   gcoord  [B, N, Kg]      contiguous, Kg >= 2: the gather's coordinates, scaled by gscale[2] as in smos_bilinear_gather_fwd
+ *   scoord  [B, N, Ks]      contiguous, Ks >= 2: the scatter's, cell = trunc(coord * sscale[2]) as in smos_voxel_maxpool_fwd
+ *   out     [B, C, Ho, Wo]  element strides out_stride[4]; MUST be zero-filled by the caller
+ *   pts     [B, C, N]       element strides pts_stride[3], or NULL: the gathered values, the bits of smos_bilinear_gather_fwd
+ *   flag_ws                 device int32 scratch (4 bytes), as in smos_voxel_maxpool_fwd
+ * out has the bits of the two calls it stands for, for every finite grid: a negative value takes the same exact path
+ * (two more launches that return at once otherwise). */
+int smos_gather_scatter_train_fwd(const float* grid, const int64_t* grid_stride, const float* gcoord, int32_t Kg,
+                                  const float* gscale, const float* scoord, int32_t Ks, const float* sscale, float* out,
+                                  const int64_t* out_stride, float* pts, const int64_t* pts_stride, int64_t B, int64_t C,
+                                  int64_t Hg, int64_t Wg, int64_t N, int64_t Ho, int64_t Wo, int32_t* flag_ws,
+                                  smos_stream_t stream);
+
+/* Its backward.  The gradient of the point values is
+ *   x[b, c, n] = grad_out[b, c, cell(n)] if the point is kept and its gathered value (recomputed, the forward's bits) equals
+ *                out[b, c, cell(n)], else 0 -- every tie wins, a 0 in a cell whose maximum is 0 wins, as in
+ *                smos_voxel_maxpool_bwd -- plus grad_pts[b, c, n] (one float32 addition) where grad_pts is not NULL,
+ * and grad_grid is smos_bilinear_gather_bwd of x: the same taps, weights, wave tiles and row atomics, except that a run
+ * of points whose sum is exactly 0 issues no atomic.  The sums depend on the arrival order of the atomics.
+ *   out       [B, C, Ho, Wo]  the forward's result, element strides out_stride[4]
+ *   grad_out  [B, C, Ho, Wo]  element strides grad_out_stride[4] (e.g. a channel slice of a wider tensor)
+ *   grad_pts  [B, C, N]       element strides grad_pts_stride[3], or NULL
+ *   grad_grid [B, C, Hg, Wg]  element strides grad_grid_stride[4]; may arrive uninitialised: the call zeroes it itself.
+ *                             Channel stride 1 and C >= 8: whole row segments; anything else: 4-byte atomics. */
+int smos_gather_scatter_train_bwd(const float* grid, const int64_t* grid_stride, const float* gcoord, int32_t Kg,
+                                  const float* gscale, const float* scoord, int32_t Ks, const float* sscale, const float* out,
+                                  const int64_t* out_stride, const float* grad_out, const int64_t* grad_out_stride,
+                                  const float* grad_pts, const int64_t* grad_pts_stride, float* grad_grid,
+                                  const int64_t* grad_grid_stride, int64_t B, int64_t C, int64_t Hg, int64_t Wg, int64_t N,
+                                  int64_t Ho, int64_t Wo, smos_stream_t stream);
+
+/* x itself, [B, C, N] at element strides x_stride[3], every element written and nothing else: the input of
+ * smos_bilinear_gather_bwd_det for a fixed-order backward.  Other arguments as smos_gather_scatter_train_bwd. */
+int smos_gather_scatter_train_point_grad(const float* grid, const int64_t* grid_stride, const float* gcoord, int32_t Kg,
+                                         const float* gscale, const float* scoord, int32_t Ks, const float* sscale,
+                                         const float* out, const int64_t* out_stride, const float* grad_out,
+                                         const int64_t* grad_out_stride, const float* grad_pts, const int64_t* grad_pts_stride,
+                                         float* x, const int64_t* x_stride, int64_t B, int64_t C, int64_t Hg, int64_t Wg,
+                                         int64_t N, int64_t Ho, int64_t Wo, smos_stream_t stream);
 
 /* --------------------------------------------------------------------------------------------
  * Training loss: OHEM cross-entropy + lovasz_weight * Lovasz-softmax (classes = present, one image), one scalar.

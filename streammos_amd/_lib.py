@@ -27,6 +27,11 @@ SIGNATURES = {
     "smos_segsum_chunk": [],
     "smos_bilinear_gather_bwd_det_work_bytes": [i64, i64, i64, i64, i64],
     "smos_bilinear_gather_bwd_det": [vp, c_i64p, vp, i32, vp, c_i64p, i64, i64, i64, i64, i64, c_f32p, vp, i64, vp],
+    "smos_gather_scatter_train_fwd": [vp, c_i64p, vp, i32, c_f32p, vp, i32, c_f32p, vp, c_i64p, vp, c_i64p, i64, i64, i64, i64, i64, i64, i64, vp, vp],
+    "smos_gather_scatter_train_bwd": [vp, c_i64p, vp, i32, c_f32p, vp, i32, c_f32p, vp, c_i64p, vp, c_i64p, vp, c_i64p, vp, c_i64p,
+                                      i64, i64, i64, i64, i64, i64, i64, vp],
+    "smos_gather_scatter_train_point_grad": [vp, c_i64p, vp, i32, c_f32p, vp, i32, c_f32p, vp, c_i64p, vp, c_i64p, vp, c_i64p, vp, c_i64p,
+                                             i64, i64, i64, i64, i64, i64, i64, vp],
     "smos_seg_loss_tile": [],
     "smos_seg_loss_work_bytes": [i64, i32],
     "smos_seg_loss_fwd": [vp, c_i64p, vp, i64, i32, i64, i64, ctypes.c_float, ctypes.c_float, i64, vp, vp, vp, vp, i64, vp],
@@ -133,7 +138,7 @@ INT64_RESULTS = (
     "smos_point_head_train_work_bytes", "smos_point_head_train_mask_words",
 )
 
-ABI_VERSION = 3      # SMOS_ABI_VERSION of the include/smos.h these signatures were written against
+ABI_VERSION = 4      # SMOS_ABI_VERSION of the include/smos.h these signatures were written against
 
 _lib = None
 

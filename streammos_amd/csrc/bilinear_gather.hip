@@ -12,6 +12,7 @@
 // The sums depend on the arrival order of the atomics: last bits can differ from run to run.
 #include "smos_common.h"
 #include "bilinear_taps.h"
+#include "zero_fill.h"
 
 namespace smos {
 
@@ -65,19 +66,6 @@ __global__ __launch_bounds__(kBlock) void bil_rows(const float* __restrict__ gri
 
 
 // ---- backward ----
-constexpr int kBt = 32;      // points per wave tile
-constexpr int kBPitch = 66;  // floats per LDS row: the fill's lane (p, h) writes bank (2 p + 2 j + h) mod 64, all different
-
-__device__ __forceinline__ void bwd_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float lane_f(float v, int i) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i));
-}
-
 // lane = point, loop over channels: 4-byte atomics at the destination's strides (C < 8, or a destination that is not
 // channels-last).  BilGeom: gs_* = grad_grid strides, os_* = grad_out strides.  The trip count is the same for every
 // lane; a lane past the end works on the last point (clamped address) and its adds are masked: no load sits under a
@@ -184,23 +172,6 @@ __global__ __launch_bounds__(kBlock) void bil_bwd_rows(const float* __restrict__
   }
 }
 
-// zero fill of a destination that is not one dense block: dims sorted by stride, the smallest last
-struct ZeroGeom {
-  int64_t size[4], stride[4];
-};
-__global__ __launch_bounds__(kBlock) void bil_bwd_zero(float* __restrict__ p, ZeroGeom z, int64_t total) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t r = i, off = 0;
-#pragma unroll
-    for (int d = 3; d >= 0; --d) {
-      const int64_t q = r / z.size[d];
-      off += (r - q * z.size[d]) * z.stride[d];
-      r = q;
-    }
-    p[off] = 0.0f;
-  }
-}
-
 }  // namespace smos
 
 using namespace smos;
@@ -256,33 +227,9 @@ extern "C" int smos_bilinear_gather_bwd(const float* grad_out, const int64_t* gr
   g.gs_b = grad_grid_stride[0]; g.gs_c = grad_grid_stride[1]; g.gs_h = grad_grid_stride[2]; g.gs_w = grad_grid_stride[3];
   hipStream_t s = (hipStream_t)stream;
 
-  // the destination arrives uninitialised: one dense block is a memset, anything else a strided fill
-  ZeroGeom z;
+  // the destination arrives uninitialised
   const int64_t size[4] = {B, C, H, W};
-  int order[4] = {0, 1, 2, 3};
-  for (int i = 1; i < 4; ++i)
-    for (int j = i; j > 0 && grad_grid_stride[order[j]] > grad_grid_stride[order[j - 1]]; --j) {
-      const int tmp = order[j]; order[j] = order[j - 1]; order[j - 1] = tmp;
-    }
-  bool dense = true;
-  int64_t expect = 1;
-  for (int d = 3; d >= 0; --d) {
-    z.size[d] = size[order[d]];
-    z.stride[d] = grad_grid_stride[order[d]];
-    SMOS_REQUIRE(z.stride[d] >= 0, "bilinear_gather_bwd: negative destination stride");
-    if (z.size[d] > 1) {
-      dense = dense && z.stride[d] == expect;
-      expect *= z.size[d];
-    }
-  }
-  const int64_t total = B * C * H * W;
-  if (dense) {
-    if (hipMemsetAsync(grad_grid, 0, (size_t)total * sizeof(float), s) != hipSuccess) return check_launch("bilinear_gather_bwd memset");
-  } else {
-    hipLaunchKernelGGL(bil_bwd_zero, dim3(grid_for(total, kBlock, 256 * 16)), dim3(kBlock), 0, s, grad_grid, z, total);
-    const int rc = check_launch("bilinear_gather_bwd zero");
-    if (rc != SMOS_OK) return rc;
-  }
+  if (int rc = zero_destination(grad_grid, grad_grid_stride, size, s, "bilinear_gather_bwd zero")) return rc;
   if (N == 0) return SMOS_OK;
   SMOS_REQUIRE(grad_out && coord && grad_out_stride && scale, "bilinear_gather_bwd: null pointer");
   g.os_b = grad_out_stride[0]; g.os_c = grad_out_stride[1]; g.os_n = grad_out_stride[2];

@@ -1,6 +1,6 @@
 // Position side of the grid -> point bilinear gather: geometry, the float32 pixel position and the four taps.  One
 // definition for the forward and the atomic backward (csrc/bilinear_gather.hip) and for the fixed-order backward
-// (csrc/segsum.hip): the same taps and weights to the bit.
+// (csrc/segsum.hip) and for the fused training transfers (csrc/gather_scatter_train.hip): the same taps and weights to the bit.
 #pragma once
 #include "smos_common.h"
 
@@ -51,6 +51,20 @@ __device__ __forceinline__ Taps make_taps(const float* __restrict__ crow, const 
   t.y0 = y0;
   t.x0 = x0;
   return t;
+}
+
+// ---- wave tiles of the row-atomic backward (bil_bwd_rows, and gst_bwd_rows of csrc/gather_scatter_train.hip) ----
+constexpr int kBt = 32;      // points per wave tile
+constexpr int kBPitch = 66;  // floats per LDS row: the fill's lane (p, h) writes bank (2 p + 2 j + h) mod 64, all different
+
+__device__ __forceinline__ void bwd_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ float lane_f(float v, int i) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), i));
 }
 
 }  // namespace smos

@@ -53,7 +53,7 @@ struct KernelSetup {
 int kernel_setup(const void* fn, size_t dyn_lds_bytes, int occupancy_block, KernelSetup* out, const char* what);
 
 // smos_debug_set_conv_grid_cap: upper bound on the grid of the persistent convolution kernels, of stem_gemm (csrc/stem.hip), of
-// pointnet_scatter (csrc/point_fused.hip), of gather_scatter_cl / _cl4 (csrc/cl_kernels.hip), of point_head (csrc/point_head.hip), of tta_argmax (csrc/vote.hip), of the fixed-order backward sums (csrc/segsum.hip) and of the chunk-striding kernels of both fused training ops
+// pointnet_scatter (csrc/point_fused.hip), of gather_scatter_cl / _cl4 (csrc/cl_kernels.hip), of point_head (csrc/point_head.hip), of tta_argmax (csrc/vote.hip), of the fixed-order backward sums (csrc/segsum.hip), of the fused training transfers (csrc/gather_scatter_train.hip) and of the chunk-striding kernels of both fused training ops
 // (csrc/point_mlp_train.hip, csrc/point_head_train.hip, through chunk_grid of csrc/chunk_sums.h) (0 = none).  A test hook: it makes a block walk several work items on shapes small
 // enough to check against float64, on any CU count.
 int64_t conv_grid_cap(int64_t cap);

@@ -58,7 +58,9 @@ conv1_fused = Switch("SMOS_CONV1_TRAIN", False)
 # Whether BilinearSample trains through the own backward kernel (off: an A/B against F.grid_sample).
 bilinear_bwd_own = Switch("SMOS_BILINEAR_BWD", True)
 set_deterministic, set_point_mlp_fused, set_point_head_fused = is_deterministic.set, point_mlp_fused.set, point_head_fused.set
-set_conv1_fused, set_bilinear_bwd_own = conv1_fused.set, bilinear_bwd_own.set
+# Whether CENet_Transformer._cross_view may send its four transfers (BilinearSample -> VoxelMaxPool) to gather_scatter_train.
+cross_view_fused = Switch("SMOS_CROSS_VIEW_TRAIN", False)
+set_conv1_fused, set_bilinear_bwd_own, set_cross_view_fused = conv1_fused.set, bilinear_bwd_own.set, cross_view_fused.set
 
 
 def _require_cuda(name, *tensors):
@@ -233,6 +235,134 @@ def bilinear_gather(grid, coord, scale, out=None, point_major=False):
     if grad_mode and grid.requires_grad:
         return _BilinearGather.apply(grid, coord, scale, (out,), point_major)
     return _bilinear_gather_fwd(grid, coord, scale, out, point_major)
+
+
+def _gst_coord(t):
+    """[B,N,K(,1)] coordinates as the contiguous [B,N,K] the kernels read"""
+    if t.dim() == 4:
+        t = t[..., 0]
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _gst_common(grid, gcoord, gscale, scoord, sscale, out):
+    """The leading arguments of the three smos_gather_scatter_train_* entries up to out's strides, and their trailing sizes."""
+    b, c, hg, wg = grid.shape
+    head = (grid.data_ptr(), _lib.i64_array(grid.stride()), gcoord.data_ptr(), gcoord.shape[2], _lib.f32_array(gscale),
+            scoord.data_ptr(), scoord.shape[2], _lib.f32_array(sscale), out.data_ptr(), _lib.i64_array(out.stride()))
+    return head, (b, c, hg, wg, gcoord.shape[1], out.shape[2], out.shape[3])
+
+
+def _gst_strides(t):
+    return None if t is None else _lib.i64_array(t.stride())
+
+
+def _gather_scatter_train_fwd(grid, gcoord, gscale, scoord, out_size, sscale, want_points):
+    b, c = grid.shape[:2]
+    n = gcoord.shape[1]
+    out = torch.zeros((b, c) + out_size, dtype=torch.float32, device=grid.device)
+    pts = torch.empty((b, c, n), dtype=torch.float32, device=grid.device) if want_points else None
+    flag = shared.get("maxpool_flag", (4,), torch.int32, grid.device, zero=True)
+    head, sizes = _gst_common(grid, gcoord, gscale, scoord, sscale, out)
+    with _on(grid.device), profiling.span_f("gather_scatter_train_fwd[%dx%dx%dx%d->%d->%dx%d]", sizes):
+        _lib.call("smos_gather_scatter_train_fwd", *head, _ptr(pts), _gst_strides(pts), *sizes, flag.data_ptr(), _stream(grid))
+    return out, pts
+
+
+def gather_scatter_train_point_grad(grid, gcoord, gscale, scoord, sscale, out, grad_out, grad_pts=None, x=None):
+    """The gradient of the point values of ``gather_scatter_train`` as a tensor x [B,C,N] (smos_gather_scatter_train_point_grad):
+    grad_out at the point's cell where the point is kept and its recomputed value equals ``out`` there, else 0, plus
+    ``grad_pts``.  x: where to write it (any strides), else a fresh tensor."""
+    _require_cuda("gather_scatter_train_point_grad", grid, gcoord, scoord, out, grad_out, grad_pts, x)
+    gcoord, scoord = _gst_coord(gcoord), _gst_coord(scoord)
+    head, sizes = _gst_common(grid, gcoord, gscale, scoord, sscale, out)
+    if x is None:
+        x = torch.empty((sizes[0], sizes[1], sizes[4]), dtype=torch.float32, device=grid.device)
+    with _on(grid.device), profiling.span_f("gather_scatter_train_point_grad[%dx%dx%dx%d->%d->%dx%d]", sizes):
+        _lib.call("smos_gather_scatter_train_point_grad", *head, grad_out.data_ptr(), _lib.i64_array(grad_out.stride()),
+                  _ptr(grad_pts), _gst_strides(grad_pts), x.data_ptr(), _lib.i64_array(x.stride()), *sizes, _stream(grid))
+    return x
+
+
+def gather_scatter_train_backward(grid, gcoord, gscale, scoord, sscale, out, grad_out, grad_pts=None, channels_last=True,
+                                  deterministic=None):
+    """Gradient of ``gather_scatter_train`` with respect to its grid, [B,C,Hg,Wg]: channels-last strides (row atomics) or
+    NCHW-contiguous (4-byte atomics), as ``bilinear_gather_backward``.  One launch (smos_gather_scatter_train_bwd; a run of
+    points whose sum is exactly 0 issues no atomic), or with ``deterministic`` (None: ``is_deterministic()``) the point
+    gradient into scratch (``gather_scatter_train_point_grad``) and the fixed-order sum of ``bilinear_gather_backward``: the
+    bits of the module path in that mode."""
+    _require_cuda("gather_scatter_train_backward", grid, gcoord, scoord, out, grad_out, grad_pts)
+    gcoord, scoord = _gst_coord(gcoord), _gst_coord(scoord)
+    head, sizes = _gst_common(grid, gcoord, gscale, scoord, sscale, out)
+    b, c, hg, wg, n = sizes[:5]
+    if is_deterministic() if deterministic is None else deterministic:
+        x = shared.get("cross_view_point_grad", (b, c, n), torch.float32, grid.device)
+        gather_scatter_train_point_grad(grid, gcoord, gscale, scoord, sscale, out, grad_out, grad_pts, x=x)
+        return bilinear_gather_backward(x, gcoord, gscale, (b, c, hg, wg), channels_last=channels_last, deterministic=True)
+    if channels_last:
+        grad_grid = torch.empty((b, hg, wg, c), dtype=torch.float32, device=grid.device).permute(0, 3, 1, 2)
+    else:
+        grad_grid = torch.empty((b, c, hg, wg), dtype=torch.float32, device=grid.device)
+    with _on(grid.device), profiling.span_f("gather_scatter_train_bwd[%dx%dx%dx%d<-%d<-%dx%d]", sizes):
+        _lib.call("smos_gather_scatter_train_bwd", *head, grad_out.data_ptr(), _lib.i64_array(grad_out.stride()), _ptr(grad_pts),
+                  _gst_strides(grad_pts), grad_grid.data_ptr(), _lib.i64_array(grad_grid.stride()), *sizes, _stream(grid))
+    return grad_grid
+
+
+class _GatherScatterTrain(torch.autograd.Function):
+    """ops.gather_scatter_train.  Kept for the backward: the source grid, the two coordinate tensors and out -- never a
+    [B,C,N] tensor; nothing at all where grid needs no gradient."""
+
+    @staticmethod
+    def forward(ctx, grid, gcoord, scoord, gscale, out_size, sscale, want_points):
+        out, pts = _gather_scatter_train_fwd(grid, gcoord, gscale, scoord, out_size, sscale, want_points)
+        ctx.set_materialize_grads(False)           # a result nobody used arrives as None, not as a [B,C,N] tensor of zeros
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(grid, gcoord, scoord, out)
+            ctx.scales = (gscale, sscale)
+        return (out, pts) if want_points else out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, grad_pts=None):
+        if grad_out is None and grad_pts is None:
+            return (None,) * 7
+        grid, gcoord, scoord, out = ctx.saved_tensors
+        gscale, sscale = ctx.scales
+        if grad_out is None:                       # only the point values were used
+            grad_out = torch.zeros_like(out)
+        return (gather_scatter_train_backward(grid, gcoord, gscale, scoord, sscale, out, grad_out, grad_pts),
+                None, None, None, None, None, None)
+
+
+def gather_scatter_train(grid, gcoord, gscale, scoord, out_size, sscale, want_points=False):
+    """One cross-view transfer of training as one autograd op: ``BilinearSample(scale_rate=gscale)(grid,
+    gcoord)`` followed by ``VoxelMaxPool(., scoord, out_size, sscale)``, to the bit, without the [B,C,N] tensor between them.
+
+    grid [B,C,Hg,Wg] float32 on the GPU, any strides; gcoord, scoord [B,N,K>=2(,1)] float32, without gradient; out_size
+    (Ho, Wo).  Returns out [B,C,Ho,Wo] (NCHW-contiguous), or (out, pts [B,C,N]) with ``want_points``: the gathered values,
+    which carry the graph too.  The backward recomputes each point's value from the saved grid, takes the gradient of the
+    cells the point wins and adds the rows of winners only (``gather_scatter_train_backward``); it returns the gradient of
+    grid with channels-last strides, like ``bilinear_gather``'s."""
+    name = "gather_scatter_train"
+    _require_cuda(name, grid, gcoord, scoord)
+    if grid.dtype != torch.float32 or gcoord.dtype != torch.float32 or scoord.dtype != torch.float32:
+        raise RuntimeError("%s: float32 only (got %s, %s, %s)" % (name, grid.dtype, gcoord.dtype, scoord.dtype))
+    if gcoord.requires_grad or scoord.requires_grad:
+        raise RuntimeError("%s: no gradient with respect to the coordinates (they are data); detach them" % name)
+    gcoord, scoord = _gst_coord(gcoord), _gst_coord(scoord)
+    out_size = tuple(int(v) for v in out_size)
+    gscale, sscale = tuple(float(v) for v in gscale), tuple(float(v) for v in sscale)
+    if (grid.dim() != 4 or gcoord.dim() != 3 or scoord.dim() != 3 or gcoord.shape[0] != grid.shape[0] or gcoord.shape[2] < 2
+            or scoord.shape[2] < 2 or tuple(scoord.shape[:2]) != tuple(gcoord.shape[:2]) or len(out_size) != 2 or len(gscale) != 2
+            or len(sscale) != 2 or min(out_size) < 1 or grid.shape[2] < 1 or grid.shape[3] < 1):
+        raise RuntimeError("%s: shape mismatch grid %s gcoord %s scoord %s out_size %s"
+                           % (name, tuple(grid.shape), tuple(gcoord.shape), tuple(scoord.shape), out_size))
+    if gcoord.device != grid.device or scoord.device != grid.device:
+        raise RuntimeError("%s: coordinates on %s / %s, grid on %s" % (name, gcoord.device, scoord.device, grid.device))
+    if torch.is_grad_enabled() and grid.requires_grad:
+        return _GatherScatterTrain.apply(grid, gcoord, scoord, gscale, out_size, sscale, bool(want_points))
+    out, pts = _gather_scatter_train_fwd(grid, gcoord, gscale, scoord, out_size, sscale, bool(want_points))
+    return (out, pts) if want_points else out
 
 
 def seg_loss_tile():

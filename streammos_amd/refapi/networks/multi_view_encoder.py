@@ -179,9 +179,32 @@ class CENet_Transformer(nn.Module):
         mods.append(block(out_planes, dilation=dilation, use_att=True))
         return nn.Sequential(*mods)
 
-    def _cross_view(self, bev, bev_xy, sphere, sampler, rv_net, rv_size, bev_size, scale):
+    def _cross_view_fused(self, bev, bev_xy, sphere, sampler):
+        """Whether _cross_view sends its two transfers through ops.gather_scatter_train: the switch is on (ops.cross_view_fused,
+        SMOS_CROSS_VIEW_TRAIN, default 0), the map and both coordinate tensors are CUDA float32, the coordinates are [B,N,K,1]
+        without gradient, the sampler is a BilinearSample, no autocast, and the module trains or gradients are enabled.
+        Everything else stays on the modules."""
+        if not ops.cross_view_fused() or type(sampler) is not backbone.BilinearSample:
+            return False
+        if not (torch.is_tensor(bev) and bev.is_cuda and bev.dtype == torch.float32 and bev.dim() == 4 and bev.numel() > 0):
+            return False
+        for t in (bev_xy, sphere):
+            if not (torch.is_tensor(t) and t.device == bev.device and t.dtype == torch.float32 and t.dim() == 4 and t.shape[3] == 1
+                    and t.shape[2] >= 2 and t.shape[0] == bev.shape[0] and t.shape[1] == bev_xy.shape[1] and not t.requires_grad):
+                return False
+        return not torch.is_autocast_enabled() and (self.training or torch.is_grad_enabled())
+
+    def _cross_view(self, bev, bev_xy, sphere, sampler, rv_net, rv_size, bev_size, scale, want_points=True):
         """B2P gather -> P2R scatter -> range-view convs -> R2P gather -> P2B scatter
-        (multi_view_encoder.py:395-405 and :410-420)."""
+        (multi_view_encoder.py:395-405 and :410-420).  want_points: whether the caller uses the second result, the point
+        features of the way back."""
+        if self._cross_view_fused(bev, bev_xy, sphere, sampler):
+            # each gather + scatter pair as one op that stores no [B,C,N] tensor (ops.gather_scatter_train, DESIGN.md 4.15b);
+            # only the point features somebody reads are written
+            rv = rv_net(ops.gather_scatter_train(bev, bev_xy, sampler.scale_rate, sphere, rv_size, scale))
+            back = ops.gather_scatter_train(rv, sphere, sampler.scale_rate, bev_xy, bev_size, scale, want_points=want_points)
+            back, pts = back if want_points else (back, None)
+            return torch.cat((bev, back), dim=1), (None if pts is None else pts.unsqueeze(-1))
         pts = sampler(bev, bev_xy)
         rv = rv_net(VoxelMaxPool(pcds_feat=pts, pcds_ind=sphere, output_size=rv_size, scale_rate=scale))
         pts = sampler(rv, sphere)
@@ -213,7 +236,7 @@ class CENet_Transformer(nn.Module):
                 return_query=False):
         x0 = self.header_bev(x)
         x0, _ = self._cross_view(x0, pcds_cood_cur, pcds_sphere_coord_cur, self.bev_grid2point_x0, self.header_rv,
-                                 (32, 1024), (256, 256), (0.5, 0.5))
+                                 (32, 1024), (256, 256), (0.5, 0.5), want_points=False)
         x1 = self.res1_bev(x0)
         x1, x1_point = self._cross_view(x1, pcds_cood_cur, pcds_sphere_coord_cur, self.bev_grid2point_x1, self.res1_rv,
                                         (16, 512), (128, 128), (0.25, 0.25))
