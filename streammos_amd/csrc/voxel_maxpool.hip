@@ -14,6 +14,8 @@
 //    return immediately while the flag is clear then redo the exact reference algorithm (racing
 //    member store, then signed-max / unsigned-min on the bit pattern).  The model never takes it: all
 //    five call sites scatter post-ReLU features (models/StreamMOS.py:102, multi_view_encoder.py:396-419).
+//    A NaN raises the flag too (the test is "neither positive nor zero"), so it takes the exact path: a cell whose only
+//    member is NaN ends as NaN whether or not another point of the tensor is negative, as in the reference.
 //  * Two lane mappings, chosen from the strides on the host:
 //      "points": one lane per point, loop over channels  -> coalesced reads of channel-major [C,N]
 //                features (the reference layout), scattered 4-byte atomics;
@@ -56,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void vmp_fwd_points(const float* __restrict
       for (int k = 0; k < 8; ++k) {
         if (v[k] > 0.0f)
           atomicMax(reinterpret_cast<int*>(out + off + (int64_t)(c + k) * g.out_c), __float_as_int(v[k]));
-        else if (v[k] < 0.0f)
+        else if (!(v[k] == 0.0f))
           saw_neg = 1;
       }
     }
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(kBlock) void vmp_fwd_points(const float* __restrict
       float v = f[(int64_t)c * g.fs_c];
       if (v > 0.0f)
         atomicMax(reinterpret_cast<int*>(out + off + (int64_t)c * g.out_c), __float_as_int(v));
-      else if (v < 0.0f)
+      else if (!(v == 0.0f))
         saw_neg = 1;
     }
   }
@@ -96,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void vmp_fwd_rows(const float* __restrict__
       float v = f[c];
       if (v > 0.0f)
         atomicMax(reinterpret_cast<int*>(out + off + c), __float_as_int(v));
-      else if (v < 0.0f)
+      else if (!(v == 0.0f))
         saw_neg = 1;
     }
   }
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void vmp_fwd_signed(const float* __restrict
         // the cell now holds a real member: signed max for v >= 0 beats any negative pattern, unsigned
         // min among negative patterns picks the smallest magnitude and never displaces a non-negative
         if (v >= 0.0f)
-          atomicMax(reinterpret_cast<int*>(p), __float_as_int(v));
+          atomicMax(reinterpret_cast<int*>(p), __float_as_int(v) & 0x7fffffff);  // -0.0 is a zero: as an integer it would lose to every negative
         else
           atomicMin(reinterpret_cast<unsigned int*>(p), __float_as_uint(v));
       }
@@ -172,7 +174,7 @@ struct VmpNum<double> {
   static __device__ __forceinline__ bool is_nan(double v) { return v != v; }
   static __device__ __forceinline__ void atom_max(double* p, double v) {
     if (v >= 0.0)
-      atomicMax(reinterpret_cast<long long*>(p), __double_as_longlong(v));
+      atomicMax(reinterpret_cast<long long*>(p), __double_as_longlong(v) & 0x7fffffffffffffffLL);  // -0.0 counts as a zero
     else
       atomicMin(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v));
   }
