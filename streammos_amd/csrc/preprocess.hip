@@ -31,6 +31,12 @@ __global__ __launch_bounds__(kBlock) void prep_transform_mask(const float* __res
       x = (float)pose_row_f64(pose.m + 0, dx, dy, dz);
       y = (float)pose_row_f64(pose.m + 4, dx, dy, dz);
       z = (float)pose_row_f64(pose.m + 8, dx, dy, dz);
+    } else {
+      // the host path multiplies by the identity and adds its zero translation: a raw -0 comes out as +0.  The sign decides
+      // the branch of atan2f(x, y) at y < 0 (range-image column 0 against 2048), so the shortcut has to drop it too.
+      x = __fadd_rn(x, 0.0f);
+      y = __fadd_rn(y, 0.0f);
+      z = __fadd_rn(z, 0.0f);
     }
     reinterpret_cast<float4*>(moved)[i] = make_float4(x, y, z, p.w);
     mask[i] = (x >= g.lo[0] && x < g.hi[0] && y >= g.lo[1] && y < g.hi[1] && z >= g.lo[2] && z < g.hi[2]) ? 1 : 0;
